@@ -29,10 +29,16 @@ step over xGMI through the peer areas, inside the stream kernel's QN waves
 all-reduce if the peer path's set-up check fails -- `comm` in the line says
 which).
 
-After the headline (one GPU only) two sub-records run in the same process,
-each with its own roofline and CPU baseline: `dense_c5` (configs[4], the
-fp64 MFMA path) and `famB` (SURVEY 8d family B, the ambiguous automaton that
-runs on the traversal tiers).
+A plain run sets up, warms up, times the steps and prints the headline record
+(its roofline is arithmetic on the timed steps' own kernel times, no further
+run).  `--dump-outputs DIR` writes what the last timed step left (see
+dump_outputs).  Everything else is behind `--full`: the same steps with the
+rmin info column, the steps through the host binding (`boundary`), the CPU
+baselines with the log-likelihood's relative error, and (one GPU only) the
+sub-records that run in the same process after the headline, each with its
+own roofline and CPU baseline: `dense_c5` (configs[4], the fp64 MFMA path;
+`dense_c5_rocblas` the same with rocBLAS dgemm) and `famB` (SURVEY 8d family
+B, the ambiguous automaton that runs on the traversal tiers).
 
 Prints ONE JSON line (rank 0).
 """
@@ -80,13 +86,20 @@ def parse():
     ap.add_argument("--max-len", type=int, default=128)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--info-rmin", action="store_true",
-                    help="time the headline steps with the rmin info column on (default: measured in a "
-                         "second pass and reported as info_rmin; SURVEY 8d's timed region leaves it out)")
+                    help="time the headline steps with the rmin info column on (default: off; --full measures "
+                         "it in a second pass and reports it as info_rmin; SURVEY 8d's timed region leaves it out)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the rmin pass, the host-binding steps, the CPU baselines "
+                         "and the dense_c5 / famB sub-records (default: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="strings timed through the CPU oracle (0 = skip)")
-    ap.add_argument("--no-sub", action="store_true", help="skip the dense_c5 / famB sub-records")
+                    help="with --full: strings timed through the CPU oracle (0 = skip)")
+    ap.add_argument("--no-sub", action="store_true",
+                    help="with --full: skip the rmin pass and the dense_c5 / famB sub-records")
     ap.add_argument("--boundary-steps", type=int, default=50,
-                    help="steps timed through the host binding (wfsa_dev_objective_grad per step; 0 = skip)")
+                    help="with --full: steps timed through the host binding (wfsa_dev_objective_grad per step; "
+                         "0 = skip)")
     ap.add_argument("--profile-traffic", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="committed PMC traffic measurement to quote (if present)")
     return ap.parse_args()
@@ -290,9 +303,26 @@ def run_workload(wl, world, rank, local_rank, distributed, dist, torch, info_rmi
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dict(wl=wl, syn=syn, sym=sym, off=off, wt=wt, fsa=fsa, lrn=lrn, info=info, st0=st0, st1=st1, dt=dt,
-                t_build=t_build, barrier=barrier,
+                t_build=t_build, barrier=barrier, rows=rows, info_rmin=info_rmin,
                 value=info["n_strings"] * wl["steps"] / dt, ms_per_step=dt * 1e3 / wl["steps"],
                 local_sym=int(off[info["shard_end"]] - off[info["shard_begin"]]))
+
+
+def dump_outputs(m, out_dir):
+    """what a caller of the timed path holds after its last step, as float64
+    DIR/<name>.npy: `info_row` (the last step's info row as Run returned it:
+    KL, gradient error, g_min, g_max, lambda_min, and with --info-rmin the two
+    rmin columns, which the steps leave unset otherwise), `x` (the weights that
+    step left) and `grad` (the gradient it evaluated).  A few thousand values
+    in all; the corpus, the automaton and the start point are functions of the
+    arguments (--seed), so two builds run with the same arguments compare
+    output for output."""
+    lrn = m["lrn"]
+    os.makedirs(out_dir, exist_ok=True)
+    row = np.asarray(m["rows"][-1] if m["rows"] else [], dtype=np.float64)
+    arrays = {"info_row": row if m["info_rmin"] else row[:5], "x": lrn.x(), "grad": lrn.last_grad()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def workload_label(wl, off):
@@ -474,6 +504,8 @@ def main():
     wl = workload_args(args, args.workload, world)
     m = run_workload(wl, world, rank, local_rank, distributed, dist, torch, info_rmin=args.info_rmin)
     lrn, st1 = m["lrn"], m["st1"]
+    if args.dump_outputs and rank == 0:   # (x and the gradient are the same on every rank)
+        dump_outputs(m, args.dump_outputs)
     traffic = None
     if not wl["dense"] and wl["emissions"] == 1 and os.path.exists(args.profile_traffic):
         try:
@@ -486,7 +518,7 @@ def main():
     # GetOptimizationInfo's smallest relative path probability), which the
     # reference prints each epoch but computes outside OptimizationStep
     rmin_pass = None
-    if not args.info_rmin and not distributed and not wl["dense"] and not args.no_sub:
+    if args.full and not args.info_rmin and not distributed and not wl["dense"] and not args.no_sub:
         lrn.set_info_rmin(True)
         lrn.Run(max(wl["warmup"], 10), 1.0, -1.0)   # (its set-up, then the clock back up: as the headline's warmup)
         m["barrier"]()
@@ -500,7 +532,8 @@ def main():
                              "the evaluation's bubble / traversal kernels)"}
         lrn.set_info_rmin(False)
     # (one GPU only: a sub-record must never leave ranks waiting in a collective)
-    boundary = boundary_steps(m, args.boundary_steps) if args.boundary_steps > 0 and not distributed else None
+    boundary = (boundary_steps(m, args.boundary_steps)
+                if args.full and args.boundary_steps > 0 and not distributed else None)
 
     out = {
         "metric": METRIC,
@@ -550,7 +583,7 @@ def main():
         "prepare_ms": st1["prepare_ms"],
     }
     cpu_n = wl["cpu_sample"]
-    if rank == 0 and world == 1 and cpu_n > 0:
+    if args.full and rank == 0 and world == 1 and cpu_n > 0:
         if wl["dense"]:
             out["cpu_baseline"] = cpu_baseline_trellis(m["syn"].wfsa_text, m["sym"], m["off"], m["wt"], cpu_n,
                                                        "path enumeration (the reference algorithm) is infeasible here")
@@ -567,7 +600,7 @@ def main():
     # the sub-records: configs[4] (dense, MFMA) and family B (traversal tiers)
     # (dense_c5_rocblas: the same c5 run with rocBLAS dgemm for the GEMMs, the
     # library reference for the hand-written engine's roofline fraction)
-    if not distributed and not args.no_sub and args.workload == "c3":
+    if args.full and not distributed and not args.no_sub and args.workload == "c3":
         for key in ("dense_c5", "famB", "dense_c5_rocblas"):
             name = "famB" if key == "famB" else "c5"
             sw = workload_args(args, name, 1)

@@ -11,10 +11,10 @@
 #   fbrk           fbs_kernel breakdown over the timing variants (experiments library,
 #                  tools/exp_fbs_breakdown.sh; BRK_KNOB / BRK_VARIANTS pass through)
 #   trace          rocprof kernel trace + stats of bench.py --steps 200 --no-sub
-#   driver         bench.py at the driver's setting (--steps 20 --warmup 5)
-#   default        bench.py with no arguments
-#   famb           bench.py --workload famB
-#   c5             bench.py --workload c5 (our kernels and rocBLAS)
+#   driver         bench.py --full --steps 20 --warmup 5
+#   default        bench.py --full with no other arguments
+#   famb           bench.py --full --workload famB
+#   c5             bench.py --full --workload c5 (our kernels and rocBLAS)
 #   runcost        tools/run_cost.py (per-Run fixed cost fit)
 #   summary        one line per bench JSON written by this lease
 set -o pipefail
@@ -58,16 +58,16 @@ for r in csv.DictReader(open(sys.argv[1])):
 PY
         ;;
     driver)
-        timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
+        timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > "$O/bench_driver.json" 2> "$O/bench_driver.err" \
             || { tail -20 "$O/bench_driver.err"; return 1; } ;;
     default)
-        timeout -k 10 600 python -u bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" \
+        timeout -k 10 600 python -u bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" \
             || { tail -20 "$O/bench_default.err"; return 1; } ;;
     famb)
-        timeout -k 10 600 python -u bench.py --workload famB > "$O/bench_famb.json" 2> "$O/bench_famb.err" \
+        timeout -k 10 600 python -u bench.py --full --workload famB > "$O/bench_famb.json" 2> "$O/bench_famb.err" \
             || { tail -20 "$O/bench_famb.err"; return 1; } ;;
     c5)
-        timeout -k 10 900 python -u bench.py --workload c5 > "$O/bench_c5.json" 2> "$O/bench_c5.err" \
+        timeout -k 10 900 python -u bench.py --full --workload c5 > "$O/bench_c5.json" 2> "$O/bench_c5.err" \
             || { tail -20 "$O/bench_c5.err"; return 1; } ;;
     runcost)
         timeout -k 10 600 python -u tools/run_cost.py > "$O/runcost.txt" 2>&1; local rc=$?; cat "$O/runcost.txt"; return $rc ;;

@@ -7,7 +7,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$(readlink -f "${1:-$R/gpurun_out/prof}"); shift
 ARGS=("$@")
-[ ${#ARGS[@]} -eq 0 ] && ARGS=(--steps 10 --warmup 2 --cpu-sample 0)
+[ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --steps 10 --warmup 2 --cpu-sample 0)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp || exit 1
