@@ -115,6 +115,16 @@ typedef struct {
     int32_t dense_blas;        /* dense path GEMM engine (WFSA_DENSE_ENGINE): 0 our fused MFMA kernels, 1 rocBLAS dgemm + our epilogues, 2 our split-K MFMA kernels + epilogues, 3 our LDS-DMA pipelined MFMA kernels + epilogues */
     int32_t qn_inkernel_waves; /* last device QN run: its update ran inside the stream kernel on this many waves (0: the separate QN step kernel) */
     int32_t qn_batches;        /* ... in this many batches of constraints (at most 64 members each) */
+    /* the regime of the per-iteration path, chosen at preparation from the
+     * parameter count and the structural counts */
+    int32_t stream_block;      /* threads per block of the stream kernel (512 or 1024) */
+    int32_t stream_w_lds;      /* it stages the weight table in LDS */
+    int32_t stream_wide;       /* 32-bit stream words (n_full >= 0x8000 or >= 0x7fff multi-parameter edges) */
+    int32_t stream_multi;      /* some stream word is a multi-parameter composite */
+    int32_t stream_delta;      /* it reads the delta format */
+    int32_t bubbles_fused;     /* an evaluation without log q runs the bubbles inside the stream kernel */
+    int32_t grad_tables;       /* the preparation-time gradient pass accumulates in LDS (0: per-block slabs in HBM) */
+    int32_t wave_lgrad;        /* the traversal wave kernel's gradient table is in LDS (1) or global (0); -1: no wave kernel configured */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */

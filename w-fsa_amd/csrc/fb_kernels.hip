@@ -2208,7 +2208,10 @@ __device__ __forceinline__ double min_path_log(const double (&ew)[RE], const int
 // and run; FOLD: the (min, x) pass after the backward -- VALU work beside the
 // slot stores' latency -- and a multi-bubble string's value stored for its
 // last arrival, settled at the wave's end)
-template <int N, int RE, bool RMIN = false, bool FOLD = false>
+// LZ (bubble_kernel): a.logq is the per-bubble log Z array -- the value is
+// stored at the bubble's list position and logq_bubbles_kernel adds each
+// string's in bubble order -- instead of the strings' entries it is added to
+template <int N, int RE, bool RMIN = false, bool FOLD = false, bool LZ = false>
 __device__ __forceinline__ double small_bubble(const BubbleArgs& a, const int4* __restrict__ tbl, int n, int b,
                                                int pos, unsigned long long* tr = nullptr, const RminFold* rf = nullptr,
                                                RminLane* rl = nullptr) {
@@ -2325,7 +2328,11 @@ __device__ __forceinline__ double small_bubble(const BubbleArgs& a, const int4* 
     }
     WFSA_BSTAMP(11)
     const double lz = log(Z);
-    if (a.logq) global_add(&a.logq[q[0].y], lz);
+    if (LZ) {
+        if (a.logq) a.logq[pos] = lz;
+    } else if (a.logq) {
+        global_add(&a.logq[q[0].y], lz);
+    }
     if (FOLD) {
         const double rv = min_path_log<N, RE>(ew, sd, q[0].x, uni, Z);
         rl->rv = rv;
@@ -2428,6 +2435,8 @@ __device__ __forceinline__ void rmin_arrive(const RminFold& rf, const double* sv
 // rf (the folded rmin column, or null): lane 0 settles the bubble's string
 // at once -- rare bubbles: its store retired, its string's arrival, the sum
 // by the k-th arrival -- and min-folds the candidate into (cv, ci)
+// LZ: as small_bubble's
+template <bool LZ = false>
 __device__ __forceinline__ double big_bubble(const BubbleArgs& a, int i, int* lsd, double* lw, double* lv, double* AB,
                              const RminFold* rf = nullptr, double* cv = nullptr, double* ci = nullptr,
                              RminLane* pend = nullptr) {
@@ -2491,7 +2500,11 @@ __device__ __forceinline__ double big_bubble(const BubbleArgs& a, int i, int* ls
             lv[e] = A[src] * bb * scale;
         }
         const double lz = log(Z);
-        if (a.logq) global_add(&a.logq[rec[1]], lz);
+        if (LZ) {
+            if (a.logq) a.logq[a.n_small4 + a.n_small + i] = lz;
+        } else if (a.logq) {
+            global_add(&a.logq[rec[1]], lz);
+        }
         res = p * lz;
     }
     wave_sync();
@@ -2515,16 +2528,33 @@ __global__ __launch_bounds__(kBubbleBlock) void bubble_kernel(BubbleArgs a) {
     const int gw = int(blockIdx.x) * WPB + wib;
     double ll_acc = 0.0;
     if (gw < a.n_big) {
-        ll_acc = big_bubble(a, gw, lsd[wib], lw[wib], lv[wib], lab[wib]);
+        ll_acc = big_bubble<true>(a, gw, lsd[wib], lw[wib], lv[wib], lab[wib]);
     } else {
         // class A (4 nodes / 4 edges: most bubbles) first, then class B
         const int b = int(small_entry(gw - a.n_big, lane, a.n_small4, a.n_small));
-        if (b >= 0 && b < a.n_small4) ll_acc = small_bubble<4, 4, RMIN>(a, a.sm4_tbl, a.n_small4, b, b);
+        if (b >= 0 && b < a.n_small4) ll_acc = small_bubble<4, 4, RMIN, false, true>(a, a.sm4_tbl, a.n_small4, b, b);
         else if (b >= a.n_small4)
-            ll_acc = small_bubble<8, 8, RMIN>(a, a.sm_tbl, a.n_small, b - a.n_small4, b);
+            ll_acc = small_bubble<8, 8, RMIN, false, true>(a, a.sm_tbl, a.n_small, b - a.n_small4, b);
     }
     ll_acc = wave_sum(ll_acc);
     if (lane == 0) a.ll_part[gw] = ll_acc;
+}
+
+// log q of the compiled strings with bubbles (want_logq evaluations): the
+// stream kernel stored the trivial words' sum, bubble_kernel each bubble's
+// log Z at its list position; a thread per string adds its bubbles' in bubble
+// order -- no atomics, the same bits every time
+__global__ __launch_bounds__(256) void logq_bubbles_kernel(double* __restrict__ logq, const double* __restrict__ lz,
+                                                          const int32_t* __restrict__ bpos,
+                                                          const int4* __restrict__ strs, int32_t n,
+                                                          const unsigned* halted) {
+    if (halted && *halted) return;
+    const int k = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (k >= n) return;
+    const int4 e = strs[k];   // (string, first bubble ordinal, bubbles, -)
+    double r = logq[e.x];
+    for (int b = e.y; b < e.y + e.z; ++b) r += lz[bpos[b]];
+    logq[e.x] = r;
 }
 
 // Per-iteration stream kernel: log q of every compiled string's trivial
@@ -3902,6 +3932,14 @@ hipError_t launch_bubbles(const BubbleArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(bubble_kernel<true>, dim3(unsigned((waves + WPB - 1) / WPB)), dim3(kBubbleBlock), 0, stream, a);
     else
         hipLaunchKernelGGL(bubble_kernel<false>, dim3(unsigned((waves + WPB - 1) / WPB)), dim3(kBubbleBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_logq_bubbles(double* logq, const double* lz, const int32_t* bpos, const int4* strs, int32_t n,
+                               const unsigned* halted, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(logq_bubbles_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, logq, lz, bpos, strs,
+                       n, halted);
     return hipGetLastError();
 }
 

@@ -589,7 +589,10 @@ struct BubbleArgs {
     const int32_t* big_eslot;
     double* contrib;
     double* ll_part;         // [waves in grid]
-    double* logq;            // [S] or null: log Z added to the string's entry
+    double* logq;            // null, or: bubble_kernel [n_bubbles], log Z stored at the bubble's list position
+                             // (small4, small, big; launch_logq_bubbles then adds them to the strings' log q
+                             // in bubble order); in the stream kernel [S], added to the string's entry (unused:
+                             // the bubbles are not fused when log q is wanted)
     double* rmin_acc;        // [S] or null: log(min path / Z) added to the string's entry (rmin column;
                              // small bubbles only in the RMIN kernel variants)
     double* rmin_sv;         // [n_bubbles] or null: the same value stored per bubble at its list position
@@ -847,6 +850,10 @@ int bubble_waves(int32_t n_small4, int32_t n_small, int32_t n_big);
 int fbs_qn_blocks_per_cu(int block, size_t lds);
 hipError_t launch_bubbles(const BubbleArgs& a, hipStream_t stream);
 hipError_t launch_reduce(const ReduceArgs& a, hipStream_t stream);
+// logq[string] += the log Z of its bubbles (lz[bpos[first .. first + n)]), in bubble order; strs[k] =
+// (string, first bubble ordinal, bubbles, -)
+hipError_t launch_logq_bubbles(double* logq, const double* lz, const int32_t* bpos, const int4* strs, int32_t n,
+                               const unsigned* halted, hipStream_t stream);
 // out[1 + j] = sum over k of gpart[k][j] in k order (the preparation-time gradient slabs)
 hipError_t launch_slab_sum(const double* gpart, int32_t n_slabs, int32_t n_params, double* out, hipStream_t stream);
 // out[0, n) -> host-mapped memory, then the flag (one block)

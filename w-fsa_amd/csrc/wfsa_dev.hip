@@ -295,6 +295,11 @@ struct wfsa_dev {
     DevBuf<double> rm_rs, rm_vb, rm_part, rm_res, rm_key;
     DevBuf<double> rm_sv;           // [n_bubbles] per-bubble rmin values at list positions (fused kernel)
     DevBuf<int32_t> rm_bpos;        // [n_bubbles] list position of each bubble
+    // log q of the compiled strings with bubbles (want_logq): each bubble's log Z at its list position,
+    // added per string in bubble order (launch_logq_bubbles)
+    DevBuf<double> lz_sv;           // [n_bubbles]
+    DevBuf<int4> lq_strs;           // (string, first bubble ordinal, bubbles, -)
+    int32_t lq_n = 0;
     bool rm_sv_used = false;        // the last evaluation stored per-bubble values into rm_sv
     double rm_base = 0.0;        // across ranks: global index of this rank's first loaded string
     DevBuf<int4> rm_amb;         // the ambiguous strings (path count > 1) with their bubble runs
@@ -1414,7 +1419,10 @@ int build_delta(wfsa_dev* ctx, const std::vector<int32_t>& comp, const std::vect
         dch += int64_t(kWave) * dg_len[size_t(g)];
     }
     dg_base[size_t(G)] = dch;
-    std::vector<uint32_t> hd(size_t(std::max<int64_t>(dch, 1)) * 4, 0u);
+    // (+ one row of slack: a wave the deal left without groups after the last
+    // group still loads row 0 at g_base[G], as it does in the 16-bit stream's tail)
+    const size_t dalloc = size_t(dch) + size_t(kWave);
+    std::vector<uint32_t> hd(dalloc * 4, 0u);
     parallel_for(int64_t(G), [&](int64_t b, int64_t e) {
         std::vector<uint32_t> r;
         for (int64_t g = b; g < e; ++g)
@@ -1443,7 +1451,7 @@ int build_delta(wfsa_dev* ctx, const std::vector<int32_t>& comp, const std::vect
                 });
             }
     });
-    HIP_TRY(ctx->dstream.upload(reinterpret_cast<const uint4*>(hd.data()), size_t(std::max<int64_t>(dch, 1)), s));
+    HIP_TRY(ctx->dstream.upload(reinterpret_cast<const uint4*>(hd.data()), dalloc, s));
     HIP_TRY(ctx->d_g_base.upload(dg_base.data(), dg_base.size(), s));
     HIP_TRY(ctx->d_g_len.upload(dg_len.data(), dg_len.size(), s));
     HIP_TRY(ctx->d_l_str.upload(dl_str.data(), dl_str.size(), s));
@@ -1894,6 +1902,14 @@ int prepare(wfsa_dev* ctx, int level) {
     }
     ctx->n_groups = G;
     ctx->n_compiled = nc;
+    {   // the compiled strings with bubbles, for their log q
+        std::vector<int4> strs;
+        for (int32_t str : comp)
+            if (h_nb[size_t(str)] > 0) strs.push_back(make_int4(str, b_first[size_t(str)], h_nb[size_t(str)], 0));
+        ctx->lq_n = int32_t(strs.size());
+        if (!strs.empty()) HIP_TRY(ctx->lq_strs.upload(strs.data(), strs.size(), s));
+        HIP_TRY(ctx->lz_sv.alloc(size_t(std::max<int64_t>(nbub, 1))));
+    }
 
     {   // slot layout: the QN loop's trimmed order when it is set up, else the identity
         std::vector<int32_t> order = ctx->slot_order;
@@ -2038,6 +2054,14 @@ int prepare(wfsa_dev* ctx, int level) {
     ctx->stats.bubble_words = bwords;
     ctx->stats.tier1_strings = n_tier1;
     ctx->stats.waves_per_block = ctx->cfg[0].waves_per_block;
+    ctx->stats.stream_block = ctx->i_block;
+    ctx->stats.stream_w_lds = ctx->i_tables;
+    ctx->stats.stream_wide = ctx->wide ? 1 : 0;
+    ctx->stats.stream_multi = ctx->n_multi > 0 ? 1 : 0;
+    ctx->stats.stream_delta = ctx->delta_on ? 1 : 0;
+    ctx->stats.bubbles_fused = bubbles_fused(ctx, false) ? 1 : 0;
+    ctx->stats.grad_tables = ctx->c_tables;
+    ctx->stats.wave_lgrad = ctx->w2_grid > 0 ? (ctx->w2_lgrad ? 1 : 0) : -1;
     ctx->stats.prepare_ms =
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     ctx->prep_level = 2;
@@ -2179,7 +2203,11 @@ int enqueue_bubbles(wfsa_dev* ctx, bool want_logq, const unsigned* halted, int32
         b.rmin_sv = ctx->rm_sv.ptr;
         ctx->rm_sv_used = true;
     }
+    if (want_logq) b.logq = ctx->lz_sv.ptr;   // per bubble, then per string in bubble order: no atomics
     HIP_TRY(wfsa::launch_bubbles(b, s));
+    if (want_logq)
+        HIP_TRY(wfsa::launch_logq_bubbles(ctx->logq.ptr, ctx->lz_sv.ptr, ctx->rm_bpos.ptr, ctx->lq_strs.ptr, ctx->lq_n,
+                                          halted, s));
     return WFSA_OK;
 }
 

@@ -49,6 +49,8 @@ class DevStats(C.Structure):
         ("comm_ranks", i32), ("comm_peer", i32),
         ("slot_chunks", i64), ("max_group_chunks", i32), ("wave_pull", i32),
         ("dense_blas", i32), ("qn_inkernel_waves", i32), ("qn_batches", i32),
+        ("stream_block", i32), ("stream_w_lds", i32), ("stream_wide", i32), ("stream_multi", i32),
+        ("stream_delta", i32), ("bubbles_fused", i32), ("grad_tables", i32), ("wave_lgrad", i32),
     ]
 
 
