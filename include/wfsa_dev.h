@@ -125,6 +125,7 @@ typedef struct {
     int32_t bubbles_fused;     /* an evaluation without log q runs the bubbles inside the stream kernel */
     int32_t grad_tables;       /* the preparation-time gradient pass accumulates in LDS (0: per-block slabs in HBM) */
     int32_t wave_lgrad;        /* the traversal wave kernel's gradient table is in LDS (1) or global (0); -1: no wave kernel configured */
+    int64_t ll_dot_launches;   /* step launches without the stream pass so far: the trivial words' log-likelihood as a dot product (WFSA_LL_DOT=0: none) */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */

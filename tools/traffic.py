@@ -21,10 +21,16 @@ def main():
     out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(os.path.dirname(os.path.dirname(
         os.path.abspath(__file__))), "profiles", "traffic_latest.json")
     res = summarise(d)
-    # the headline's stream kernel: the in-kernel QN variant (its last
-    # template argument true) when the run launched it, else the first one
+    # the headline's step kernel: the stream-less launch (step_dot_kernel)
+    # when the run launched it, else the stream kernel -- of either the
+    # in-kernel QN variant (step_dot_kernel<RMIN, QN, PX>; fbs_kernel's last
+    # template argument true), else the first one
+    dot = [k for k in res if k.startswith("step_dot_kernel")]
     fbs = [k for k in res if k.startswith("fbs_kernel")]
-    kern = next((k for k in fbs if k.replace(" ", "").endswith(",true>")), fbs[0])
+    if dot:
+        kern = next((k for k in dot if k.replace(" ", "").endswith(",true,false>")), dot[0])
+    else:
+        kern = next((k for k in fbs if k.replace(" ", "").endswith(",true>")), fbs[0])
     fetch_kib = res[kern]["FETCH_SIZE"]
     write_kib = res[kern]["WRITE_SIZE"]
     cal_r = res["stream_read"]["FETCH_SIZE"] * 1024.0
@@ -43,7 +49,7 @@ def main():
             "write_factor": fw,
         },
         "hbm_bytes_per_launch": fetch_kib * 1024.0 * fr + write_kib * 1024.0 * fw,
-        "source": os.path.abspath(d),
+        "source": os.path.basename(os.path.abspath(d)),
     }
     json.dump(rec, open(out, "w"), indent=1)
     print(json.dumps(rec, indent=1))

@@ -2952,7 +2952,7 @@ __global__ __launch_bounds__(1024, (DBG == 10 ? 8 : 1)) WFSA_FBS_ATTR void fbs_k
     // for (the halted flag, the wave's stream setup, the first row set): at
     // entry these scalar load chains took ~2 us ahead of the table's loads
     constexpr int kTB = 12;   // 16-byte pieces per thread and round (one round for 12k-entry tables at 512 threads)
-    const bool pre = DELTA && !a.no_streams && DBG != 4 && DBG != 11;
+    const bool pre = DELTA && DBG != 4 && DBG != 11;
     const int tlast = a.n_params - 1;
     // A piece is slots (s2, s2 + 1): weights j0 = s2 - 1 - s2 / kDeltaPeriod
     // and j0 + 1 whenever neither slot is a zero slot, and on a period
@@ -3005,7 +3005,7 @@ __global__ __launch_bounds__(1024, (DBG == 10 ? 8 : 1)) WFSA_FBS_ATTR void fbs_k
 #pragma unroll
         for (int d = 0; d < D; ++d) r[d] = st[int64_t(kWave) * min(c0 + d, last)];
     };
-    const bool kStreams = DBG != 3 && DBG != 4 && !a.no_streams;   // (timing experiments; bubbles-only launches)
+    const bool kStreams = DBG != 3 && DBG != 4;   // (timing experiments)
     // the first row set in flight from the start (its latency hides behind
     // the staging and the bubbles)
     if (kStreams) load(A, 0);
@@ -3100,7 +3100,7 @@ __global__ __launch_bounds__(1024, (DBG == 10 ? 8 : 1)) WFSA_FBS_ATTR void fbs_k
             if (WFSA_BIG_PRIO) __builtin_amdgcn_s_setprio(0);
         }
     };
-    if (!DELTA && W_LDS && DBG != 4 && !a.no_streams) {
+    if (!DELTA && W_LDS && DBG != 4) {
         // stage w[0, n_params] in 16-byte pieces, all of a thread's loads
         // issued before its first store (loads and stores unconditional --
         // an index past the end is clamped to the last piece, which is then
@@ -3352,7 +3352,7 @@ __global__ __launch_bounds__(1024, (DBG == 10 ? 8 : 1)) WFSA_FBS_ATTR void fbs_k
     // this block's slice of the per-edge weights and the zeroed result, for
     // the kernels after this one (nothing in this launch reads them; skipped
     // when the QN update rides in the launch)
-    if (W_LDS && !a.no_streams && !a.no_slice) edge_weight_slice(a, bid, nblk);
+    if (W_LDS && !a.no_slice) edge_weight_slice(a, bid, nblk);
     const bool qn_wave = QN && w == wpb - 2 && bid < a.qw.n_waves;
     if (qn_wave) {   // this step's QN update
         const QnWave qw = WFSA_LATE_ARG(qw);
@@ -3370,6 +3370,222 @@ __global__ __launch_bounds__(1024, (DBG == 10 ? 8 : 1)) WFSA_FBS_ATTR void fbs_k
     // -- no finish left for the next launch, and the Run's last row needs no
     // finish kernel of its own.  A step the previous finish halted publishes
     // its skipped row from its QN waves instead.
+    if (self_fin && (writer || qn_wave)) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned add = unsigned(writer) + unsigned(qn_wave);
+        unsigned before = 0u;
+        if (lane == 0) before = __hip_atomic_fetch_add(a.qw.done + a.qw.parity, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        before = __shfl(before, 0, kWave);
+        if (before + add == unsigned(nblk + a.qw.n_waves) && load_wt(a.qw.halted + 1) == 0u) {
+            double info[7];
+            unsigned st = kQnRan;
+            const QnFinish fin = WFSA_LATE_ARG(qw.fin);
+            qn_finish_compute<true, true, PX>(fin, nullptr, info, st);
+            if (lane == 0) qn_finish_publish(fin, info, st);
+        }
+    }
+    WFSA_STAMP(7)
+#undef WFSA_STAMP
+}
+
+// The step launch without the stream pass, for every evaluation that does not
+// want log q.  The stream pass feeds only the log-likelihood (log q apart),
+// and the trivial words' share of it is a dot product of two parameter-length
+// vectors (ll_trivial_share, qn_device.hpp): no weight table is staged and no
+// stream is read.  The launch is fbs_kernel's geometry and roles -- the small
+// and big bubbles from entry, the arrival, the QN waves, the finish wave, the
+// self-finish, the folded rmin column, the exchange across ranks -- built from
+// the same device functions, so the slots, the trajectory and the rows are
+// fbs_kernel's bit for bit; the log-likelihood differs by the reassociation
+// of the trivial words' sum.  Wave gw adds the terms of parameters 64 gw +
+// lane (+ 64 waves, ...) to its partial: a block's ll_part slot is its waves'
+// bubbles plus their share of the dot product, whichever variant runs (the
+// in-kernel step, the separate-kernel step and objective_grad launch the same
+// geometry).  LDS: the big bubbles' staging only (bub.big_lds_off = 0).
+template <bool RMIN, bool QN, bool PX>
+__global__ __launch_bounds__(1024) void step_dot_kernel(CompiledArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = lane_id();
+    const int wpb = int(blockDim.x) / kWave;
+    const int nblk = int(gridDim.x);
+    const int nw = nblk * wpb;
+    const int bid = int(blockIdx.x);
+    const int w = int(threadIdx.x) / kWave;
+    const int gw = __builtin_amdgcn_readfirstlane(bid * wpb + w);
+#ifdef WFSA_EXPERIMENTS
+    unsigned long long* tr = a.trace ? a.trace + size_t(gw) * 16 : nullptr;   // (timing experiments)
+#define WFSA_STAMP(k) \
+    if (tr && lane == 0) tr[k] = __builtin_amdgcn_s_memrealtime();
+#else
+#define WFSA_STAMP(k)
+#endif
+    WFSA_STAMP(0)
+    if (QN && bid == 0 && threadIdx.x == 0) {   // for the next launch
+        a.qw.arrive[a.qw.parity ^ 1] = 0u;
+        if (a.qw.done) a.qw.done[a.qw.parity ^ 1] = 0u;   // (also when only a Run's last launch finishes itself)
+    }
+    // halted is written only by an earlier launch (the QN step's finish)
+    if (a.halted && *a.halted) {
+        if (QN && bid == 0 && threadIdx.x == 0) qn_publish_row(a.qw.fin, nullptr, kQnSkipped);   // (no QN kernel)
+        return;
+    }
+    __shared__ unsigned q_arrived;   // QN: this block's waves whose bubble slots have retired
+    __shared__ unsigned blk_in;      // this block's waves whose partials are in LDS (wsum, wrv, wri)
+    if (threadIdx.x == 0) {
+        blk_in = 0u;
+        if (QN) q_arrived = 0u;
+    }
+    // the wave's share of the trivial words' log-likelihood: its loads in
+    // flight from entry, waited for with the bubbles' first loads
+    double ll_acc = ll_trivial_share(a.ll_coef, a.w, a.n_params, gw * kWave + lane, nw * kWave);
+    __syncthreads();   // (the counters above; every wave is at entry: nothing waits here)
+    WFSA_STAMP(1)
+    const bool fin_wave = bid == 0 && w == wpb - 1;
+    if (fin_wave && a.fin.active) {   // the previous QN step's finish (fbs_kernel's finish wave)
+        double finfo[7];
+        unsigned fstat = kQnRan;
+        const QnFinish fin = WFSA_LATE_ARG(fin);
+        qn_finish_compute<true, false, PX>(fin, nullptr, finfo, fstat);
+        if (lane == 0) qn_finish_publish(fin, finfo, fstat);
+    }
+    bool stored = fin_wave;   // (QN: this wave's stores must retire before it arrives)
+    constexpr bool RF = RMIN && QN;   // the folded rmin column (RminFold), as in fbs_kernel
+    RminLane rm_lane{0.0, -1, 0, 0, -1};   // the lane's small bubble
+    RminLane rm_big{0.0, -1, 0, 0, -1};    // lane 0: a big bubble whose (min, x) pass is due at the wave's end
+    int rm_pos = -1;
+    double rm_cv = INFINITY, rm_ci = -1.0;
+    if (a.bub_on && !fin_wave) {   // this wave's bubbles (fbs_kernel's deal: the same chunks, the same ranks)
+        if (w < a.bub.small_wpb) {
+            stored = true;
+            const int b = int(small_entry(int64_t(w) * nblk + bid, lane, a.bub.n_small4, a.bub.n_small));
+#ifdef WFSA_EXPERIMENTS
+            unsigned long long* btr = tr;
+#else
+            unsigned long long* btr = nullptr;
+#endif
+            __builtin_amdgcn_s_setprio(2);
+            const BubbleArgs bub = WFSA_LATE_ARG(bub);
+            const RminFold rf = WFSA_LATE_ARG(rf);
+            const RminFold* rfp = RF ? &rf : nullptr;
+            RminLane* rlp = RF ? &rm_lane : nullptr;
+            if (b >= 0 && b < bub.n_small4)
+                ll_acc += small_bubble<4, 4, RMIN, RF>(bub, bub.sm4_tbl, bub.n_small4, b, b, btr, rfp, rlp);
+            else if (b >= bub.n_small4)
+                ll_acc += small_bubble<8, 8, RMIN, RF>(bub, bub.sm_tbl, bub.n_small, b - bub.n_small4, b, btr, rfp, rlp);
+            if (RF && b >= 0) {
+                rm_pos = int(b);
+                if (rm_lane.k == 1) min_pair(rm_cv, rm_ci, rm_lane.rv, double(rm_lane.str));
+            }
+            __builtin_amdgcn_s_setprio(0);
+        }
+        const int r = big_rank(bid, w, nblk, wpb, a.bub.qw_waves);
+        if (r < a.bub.n_big) {
+            stored = true;
+            const int E = a.bub.big_lds_edges;
+            char* stg = reinterpret_cast<char*>(lds) + a.bub.big_lds_off + w * big_stage_bytes(E);
+            double* lw = reinterpret_cast<double*>(stg);
+            int* lsd = reinterpret_cast<int*>(lw + E + 2 * kMaxBubbleNodes);
+            const BubbleArgs bub = WFSA_LATE_ARG(bub);
+            const RminFold rf = WFSA_LATE_ARG(rf);
+            if (WFSA_BIG_PRIO) __builtin_amdgcn_s_setprio(WFSA_BIG_PRIO);
+            for (int i = r; i < bub.n_big; i += nw - 1)
+                ll_acc += big_bubble(bub, i, lsd, lw, lw, lw + E, RF ? &rf : nullptr, &rm_cv, &rm_ci, &rm_big);
+            if (WFSA_BIG_PRIO) __builtin_amdgcn_s_setprio(0);
+        }
+    }
+    WFSA_STAMP(2)
+    // the arrival: fbs_kernel's hand-off (see the ordering note there)
+    if (QN) {
+        if (stored) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        unsigned prev = 0u;
+        if (lane == 0) prev = atomicAdd(&q_arrived, 1u);
+        prev = __shfl(prev, 0, kWave);
+        if (lane == 0 && prev == unsigned(wpb - 1)) {   // the block's last wave: one arrival for all its stores
+            const unsigned o =
+                __hip_atomic_fetch_add(a.qw.arrive + a.qw.parity, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef WFSA_EXPERIMENTS
+            if (a.trace) {
+                a.trace[size_t(blockIdx.x) * wpb * 16 + 14] = __builtin_amdgcn_s_memrealtime();
+                a.trace[size_t(blockIdx.x) * wpb * 16 + 15] = o;
+            }
+#else
+            (void)o;
+#endif
+        }
+        WFSA_STAMP(3)
+    }
+    WFSA_STAMP(4)
+    if (RF && rm_pos >= 0 && rm_lane.k > 1) {   // a multi-bubble string's arrival (its value stored: retired by now)
+        const RminFold rf = WFSA_LATE_ARG(rf);
+        rmin_arrive(rf, WFSA_LATE_ARG(bub.rmin_sv), rm_lane, rm_cv, rm_ci);
+    }
+    if (RF) {   // a big bubble's (min, x) pass (lane 0 held its index and Z; the staging is this wave's)
+        const int big = __builtin_amdgcn_readfirstlane(rm_big.big);
+        if (big >= 0) {
+            const BubbleArgs bub = WFSA_LATE_ARG(bub);
+            const RminFold rf = WFSA_LATE_ARG(rf);
+            const double z = __shfl(rm_big.rv, 0, kWave);
+            const int E = bub.big_lds_edges;
+            char* stg = reinterpret_cast<char*>(lds) + bub.big_lds_off + w * big_stage_bytes(E);
+            double* lw = reinterpret_cast<double*>(stg);
+            int* lsd = reinterpret_cast<int*>(lw + E + 2 * kMaxBubbleNodes);
+            big_bubble_min(bub, rf, big, z, lsd, lw, lw + E, rm_cv, rm_ci);
+        }
+    }
+    // one log-likelihood partial per block (the QN finish sums them)
+    __shared__ double wsum[1024 / kWave];
+    __shared__ double wrv[1024 / kWave], wri[1024 / kWave];   // (RF: the waves' rmin candidates)
+    ll_acc = wave_sum(ll_acc);
+    if (lane == 0) wsum[w] = ll_acc;
+    if (RF) {
+        // the ambiguous traversal strings (values from the kernels before this launch), strided over the grid
+        for (int i = bid * int(blockDim.x) + int(threadIdx.x); i < a.rf.n_trav; i += nblk * int(blockDim.x)) {
+            const int st = a.rf.trav[i];
+            min_pair(rm_cv, rm_ci, a.rf.rmin_log[st], double(st));
+        }
+        for (int o = 32; o > 0; o >>= 1) min_pair(rm_cv, rm_ci, __shfl_xor(rm_cv, o, kWave), __shfl_xor(rm_ci, o, kWave));
+        if (lane == 0) {
+            wrv[w] = rm_cv;
+            wri[w] = rm_ci;
+        }
+    }
+    // the block's partials: the last of its waves to get here sums them (an
+    // LDS counter, no block barrier)
+    unsigned prev_in = 0u;
+    if (lane == 0) prev_in = __hip_atomic_fetch_add(&blk_in, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+    prev_in = __builtin_amdgcn_readfirstlane(prev_in);   // (every lane active: lane 0's)
+    const bool writer = prev_in == unsigned(wpb - 1);
+    const bool self_fin = QN && a.qw.self_finish;
+    if (writer && lane == 0) {
+        double t = 0.0;
+        for (int i = 0; i < wpb; ++i) t += wsum[i];
+        if (self_fin) store_wt(a.ll_part + bid, t);   // (read by this launch's finisher)
+        else a.ll_part[bid] = t;
+        if (RF) {
+            double v = wrv[0], idx = wri[0];
+            for (int i = 1; i < wpb; ++i) min_pair(v, idx, wrv[i], wri[i]);
+            if (self_fin) {
+                store_wt(a.rf.part + 2 * bid, v);
+                store_wt(a.rf.part + 2 * bid + 1, idx);
+            } else {
+                a.rf.part[2 * bid] = v;
+                a.rf.part[2 * bid + 1] = idx;
+            }
+        }
+    }
+    // this block's slice of the per-edge weights and the zeroed result, for
+    // the kernels after this one, where fbs_kernel writes them
+    if (a.tables >= 1 && !a.no_slice) edge_weight_slice(a, bid, nblk);
+    const bool qn_wave = QN && w == wpb - 2 && bid < a.qw.n_waves;
+    if (qn_wave) {   // this step's QN update
+        const QnWave qw = WFSA_LATE_ARG(qw);
+#ifdef WFSA_EXPERIMENTS
+        qn_wave_run<PX>(qw, bid, tr);
+#else
+        qn_wave_run<PX>(qw, bid, nullptr);
+#endif
+    }
+    // self-finish, as in fbs_kernel
     if (self_fin && (writer || qn_wave)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned add = unsigned(writer) + unsigned(qn_wave);
@@ -3544,6 +3760,10 @@ hipError_t configure_kernels(int max_dynamic_lds) {
                          reinterpret_cast<const void*>(&fbs_kernel<false, true, false, 0, false, true>),
                          reinterpret_cast<const void*>(&fbs_kernel<false, true, false, 0, true, true>),
                          reinterpret_cast<const void*>(&fbs_kernel<false, true, false, 0, false, true, true>),
+                         reinterpret_cast<const void*>(&step_dot_kernel<false, false, false>),
+                         reinterpret_cast<const void*>(&step_dot_kernel<true, false, false>),
+                         reinterpret_cast<const void*>(&step_dot_kernel<false, true, false>),
+                         reinterpret_cast<const void*>(&step_dot_kernel<true, true, false>),
 #ifdef WFSA_EXPERIMENTS
                          reinterpret_cast<const void*>(&fbs_kernel<false, true, false, 1>),
                          reinterpret_cast<const void*>(&fbs_kernel<false, true, false, 3>),
@@ -3920,6 +4140,34 @@ int fbs_qn_blocks_per_cu(int block, size_t lds) {
                                                      lds) != hipSuccess)
         return 0;
     return nb;
+}
+
+// the stream-less step launch: the variant by what rides in it, as launch_compiled chooses fbs_kernel's
+hipError_t launch_step_dot(const CompiledArgs& a, int grid, int block, size_t lds, hipStream_t stream, hipEvent_t ev0,
+                           hipEvent_t ev1) {
+    if (ev0 || ev1) {   // no dispatch events inside a stream capture (the graph path records none)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) ev0 = ev1 = nullptr;
+    }
+    if (a.qw.on && a.qw.px.on && a.rf.part)   // ... across ranks (the peer exchange)
+        return go(step_dot_kernel<true, true, true>, grid, block, lds, stream, ev0, ev1, a);
+    if (a.qw.on && a.qw.px.on) return go(step_dot_kernel<false, true, true>, grid, block, lds, stream, ev0, ev1, a);
+    if (a.qw.on && a.rf.part)   // with this step's QN update and the rmin column folded in
+        return go(step_dot_kernel<true, true, false>, grid, block, lds, stream, ev0, ev1, a);
+    if (a.qw.on) return go(step_dot_kernel<false, true, false>, grid, block, lds, stream, ev0, ev1, a);
+    if (a.bub_on && a.bub.rmin_acc)
+        return go(step_dot_kernel<true, false, false>, grid, block, lds, stream, ev0, ev1, a);
+    return go(step_dot_kernel<false, false, false>, grid, block, lds, stream, ev0, ev1, a);
+}
+
+int step_dot_blocks_per_cu(int block, size_t lds, bool rmin, bool px) {
+    int nb = 0;
+    hipError_t e;
+    if (rmin && px) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_dot_kernel<true, true, true>, block, lds);
+    else if (px) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_dot_kernel<false, true, true>, block, lds);
+    else if (rmin) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_dot_kernel<true, true, false>, block, lds);
+    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, step_dot_kernel<false, true, false>, block, lds);
+    return e == hipSuccess ? nb : 0;
 }
 
 int bubble_waves(int32_t n_small4, int32_t n_small, int32_t n_big) { return n_big + int(small_chunks(n_small4, n_small)); }

@@ -732,8 +732,6 @@ struct CompiledArgs {
     int32_t wide;
     int32_t with_grad;       // accumulate the (weight-independent) trivial-word gradient
     int32_t no_slice;        // skip edge_weight_slice (nothing after this launch reads it)
-    int32_t no_streams;      // bubbles only (the pipelined QN loop's update chain): no table
-                             // staging, no stream pass, no per-edge weight slice
     // bub_on: the stream waves also evaluate the bubbles before their
     // streams (no separate bubble kernel) -- the small ones one per lane from
     // the first waves, the big ones one per wavefront from the last
@@ -753,6 +751,7 @@ struct CompiledArgs {
     double* out;             // [1 + n_params], zeroed by block 0
     double* ll_part;         // [waves in grid] (per-iteration stream kernel: [blocks])
     double* logq;            // [S] or null
+    const double* ll_coef;   // [n_params] step_dot_kernel: this rank's trivial-word gradient (ll_trivial_share)
     const unsigned* halted;  // device-resident QN run: nonzero = skip (or null)
     QnFinish fin;            // fin.active: block 0 finishes the previous QN step first
     QnWave qw;               // qw.on: this step's QN update runs in this launch
@@ -848,6 +847,11 @@ int bubble_waves(int32_t n_small4, int32_t n_small, int32_t n_big);
 // blocks of the stream kernel with the in-kernel QN update that one CU holds
 // at once (block threads, dynamic LDS bytes); 0 on error
 int fbs_qn_blocks_per_cu(int block, size_t lds);
+// the step launch without the stream pass (step_dot_kernel: evaluations that do not want log q), and the
+// blocks of its in-kernel QN variant one CU holds (rmin: the folded column, px: the exchange across ranks)
+hipError_t launch_step_dot(const CompiledArgs& a, int grid, int block, size_t lds, hipStream_t stream,
+                           hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int step_dot_blocks_per_cu(int block, size_t lds, bool rmin, bool px);
 hipError_t launch_bubbles(const BubbleArgs& a, hipStream_t stream);
 hipError_t launch_reduce(const ReduceArgs& a, hipStream_t stream);
 // logq[string] += the log Z of its bubbles (lz[bpos[first .. first + n)]), in bubble order; strs[k] =

@@ -418,6 +418,26 @@ __device__ inline void qn_finish_publish(const QnFinish& f, const double* info, 
     qn_publish_row(f, info, status);
 }
 
+// The trivial words' part of the log-likelihood as a dot product.  A trivial
+// word's posterior is 1 whatever the weights, so sum_s p_s sum_{j in
+// trivial(s)} w_j = sum_j w_j c_j with c_j = sum_s p_s count_sj = -coef[j],
+// this rank's trivial-word gradient, constant for a prepared corpus (the
+// preparation-time gradient pass).  A lane's share: parameters first, first +
+// stride, ... below n, in that order -- the whole sum's order is a function of
+// n and the launch geometry alone.  A parameter Trim dropped has weight -inf
+// and coefficient 0: its term is selected, never multiplied (0 * -inf = NaN).
+__device__ __forceinline__ double ll_trivial_share(const double* __restrict__ coef, const double* __restrict__ w, int n,
+                                                   int first, int stride) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int j = first; j < n; j += stride) {
+        const double c = coef[j], wj = w[j];
+        const double t = c * wj;
+        s -= c != 0.0 ? t : 0.0;
+    }
+    return s;
+}
+
 template <bool PX = false>
 __device__ inline void qn_finish(const QnFinish& f, double* red) {
     double info[7];

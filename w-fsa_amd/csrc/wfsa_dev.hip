@@ -196,6 +196,8 @@ struct wfsa_dev {
     int i_block = 1024;
     size_t i_lds = 0;
     DevBuf<double> fixed_grad;       // [n_params] gradient of the trivial words (constant)
+    DevBuf<double> fixed_local;      // [n_params] this rank's own part of it (fixed_grad before the sum over the
+                                     // ranks): the coefficients of the trivial words' log-likelihood (ll_dot)
     DevBuf<double> fixed_t;          // [qn_n] the same in trimmed order (QN runs)
     bool fixed_t_on = false;
     int64_t fixed_t_key = -1;        // (prep_gen, qn setup) the gather above was made for
@@ -325,6 +327,11 @@ struct wfsa_dev {
     // the per-iteration device sequence, captured once per prepared corpus
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
+    // ... and the sequence without log q where that is another one (ll_dot:
+    // the stream-less launch), so a replay takes the eager call's kernels
+    hipGraph_t graph_nq = nullptr;
+    hipGraphExec_t graph_exec_nq = nullptr;
+    bool graph_last = false;   // the last call replayed a graph
     bool graph_failed = false;
     bool use_graph = false;    // WFSA_GRAPH=1: replay a captured graph (no per-kernel timing)
     bool in_flight = false;    // between objective_grad_begin and _end
@@ -382,10 +389,12 @@ struct wfsa_dev {
     DevBuf<unsigned> qw_done;        // [2] the self-finish's arrivals, likewise
     DevBuf<unsigned> qw_go;          // [kQnMaxWaves][kQnGoStride] the QN waves' go lines (fb_kernels.hpp QnWave::go)
     size_t qw_res_lds = ~size_t(0);  // qw_resident's cache: the launch's LDS and block, blocks per CU
-    int qw_res_block = 0, qw_res_per_cu = 0;
+    int qw_res_block = 0, qw_res_per_cu = 0, qw_res_variant = -1;
     uint32_t qw_poll_limit = 0;      // polls before an in-kernel QN wave gives up (0: the kernel default)
     bool qw_poll_fault = false;      // WFSA_FAULT_QN_POLL=1 (tests): the first QN wave never sees its arrivals
     bool qw_last_self = true;        // a Run's last launch finishes its own step (WFSA_QN_LAST_SELF=0: off)
+    bool use_ll_dot = true;          // evaluations without log q skip the stream pass: the trivial words'
+                                     // log-likelihood as a dot product (step_dot_kernel; WFSA_LL_DOT=0: fbs_kernel)
     uint64_t qw_seq = 0;             // in-kernel QN launches enqueued (their parity)
     wfsa::QnWave qw_next{};          // picked up by the next stream kernel launch (qw_next.on)
     DevBuf<unsigned long long> fbs_trace;   // timing experiments (WFSA_FBS_TRACE): per-wave stamps of the last launch
@@ -995,7 +1004,7 @@ int collect_timing(wfsa_dev* ctx) {
     ctx->timing_pending = false;
     HIP_TRY(hipEventSynchronize(ctx->ev1));
     float c_ms = 0.f, fb_ms = 0.f, all_ms = 0.f;
-    if (!ctx->graph_exec && ctx->kernel_timing) {   // events inside a captured graph are not timeable
+    if (!ctx->graph_last && ctx->kernel_timing) {   // events inside a captured graph are not timeable
         HIP_TRY(hipEventElapsedTime(&c_ms, ctx->k0[0], ctx->kc[0]));
         HIP_TRY(hipEventElapsedTime(&fb_ms, ctx->k0[0], ctx->k2_kc[0] ? ctx->kc[0] : ctx->k2[0]));
     }
@@ -1007,7 +1016,7 @@ int collect_timing(wfsa_dev* ctx) {
     ctx->stats.last_compiled_ms = double(c_ms);
     ctx->stats.compiled_kernel_ms += double(c_ms);
     ctx->stats.last_call_ms = double(all_ms);
-    ctx->stats.graph = ctx->graph_exec ? 1 : 0;
+    ctx->stats.graph = ctx->graph_last ? 1 : 0;
     return WFSA_OK;
 }
 
@@ -1933,6 +1942,7 @@ int prepare(wfsa_dev* ctx, int level) {
     }
     HIP_TRY(ctx->gpart.alloc(size_t(ctx->c_grid) * size_t(std::max(ctx->n_params, 1))));
     HIP_TRY(ctx->fixed_grad.alloc(size_t(std::max(ctx->n_params, 1))));
+    HIP_TRY(ctx->fixed_local.alloc(size_t(std::max(ctx->n_params, 1))));
 
     // traversal fallback lists
     ctx->h_tier.assign(size_t(ctx->n_strings), int8_t(-1));
@@ -2031,12 +2041,17 @@ int prepare(wfsa_dev* ctx, int level) {
         if (int rc = enqueue_compiled(ctx, true, false)) return rc;
         HIP_TRY(hipMemcpyAsync(ctx->fixed_grad.ptr, ctx->out.ptr + 1, size_t(ctx->n_params) * sizeof(double),
                                hipMemcpyDeviceToDevice, s));
+        // this rank's own copy, before the sum over the ranks: every rank's
+        // log-likelihood partial takes its own strings' trivial words once
+        HIP_TRY(hipMemcpyAsync(ctx->fixed_local.ptr, ctx->out.ptr + 1, size_t(ctx->n_params) * sizeof(double),
+                               hipMemcpyDeviceToDevice, s));
         // with a communicator the constant part is summed over the ranks once
         // here; the per-step all-reduce then carries only what varies
         if (ctx->comm && ctx->n_params > 0)
             COMM_TRY(ctx, ctx->fixed_grad.ptr, size_t(ctx->n_params), wfsa::RedOp::SumF64, s);
     } else {
         HIP_TRY(hipMemsetAsync(ctx->fixed_grad.ptr, 0, size_t(std::max(ctx->n_params, 1)) * sizeof(double), s));
+        HIP_TRY(hipMemsetAsync(ctx->fixed_local.ptr, 0, size_t(std::max(ctx->n_params, 1)) * sizeof(double), s));
         if (ctx->comm && ctx->n_params > 0)   // (every rank joins the collective)
             COMM_TRY(ctx, ctx->fixed_grad.ptr, size_t(ctx->n_params), wfsa::RedOp::SumF64, s);
     }
@@ -2073,6 +2088,13 @@ int prepare(wfsa_dev* ctx, int level) {
 // edge-weight kernel unless the kernel folds that into its prologue (it does
 // when it stages w in LDS).  with_grad: the preparation-time gradient pass
 // (followed by its slab reduction into out); else the per-iteration pass.
+// One choice per prepared context: every evaluation that does not want log q
+// takes the stream-less launch (the in-kernel step, the separate-kernel step
+// and objective_grad place the same partials in the same ll_part slots).
+bool ll_dot(const wfsa_dev* ctx, bool with_grad, bool want_logq) {
+    return ctx->use_ll_dot && !with_grad && !want_logq && ctx->n_groups > 0;
+}
+
 int enqueue_compiled(wfsa_dev* ctx, bool with_grad, bool want_logq, const unsigned* halted, int slot) {
     hipStream_t s = ctx->stream;
     const int32_t np = ctx->n_params;
@@ -2114,7 +2136,11 @@ int enqueue_compiled(wfsa_dev* ctx, bool with_grad, bool want_logq, const unsign
                 c.fin.px_slot = 0;
             }
         }
-        size_t lds = with_grad ? ctx->c_lds : ctx->i_lds;
+        // without log q the stream pass is skipped: the stream-less launch
+        // (no weight table: its LDS is the big bubbles' staging alone)
+        const bool dot = ll_dot(ctx, with_grad, want_logq);
+        if (dot) c.ll_coef = ctx->fixed_local.ptr;
+        size_t lds = with_grad ? ctx->c_lds : (dot ? 0 : ctx->i_lds);
         if (!with_grad && bubbles_fused(ctx, want_logq)) {
             c.bub = bubble_args(ctx, false, halted, nullptr);
             if (c.bub.rmin_acc) {
@@ -2125,9 +2151,10 @@ int enqueue_compiled(wfsa_dev* ctx, bool with_grad, bool want_logq, const unsign
             c.bub.small_wpb = small_waves_per_block(wfsa::small_chunks(ctx->n_small4, ctx->n_small) * kWave, ctx->i_grid);
             c.bub.qw_waves = ctx->qw_waves;
             if (ctx->n_big > 0) {
+                const size_t off = dot ? 0 : big_stage_off(ctx);
                 c.bub.big_lds_edges = ctx->big_lds_edges;
-                c.bub.big_lds_off = int32_t(big_stage_off(ctx));
-                lds = big_stage_off(ctx) + size_t(ctx->i_block / kWave) * size_t(wfsa::big_stage_bytes(ctx->big_lds_edges));
+                c.bub.big_lds_off = int32_t(off);
+                lds = off + size_t(ctx->i_block / kWave) * size_t(wfsa::big_stage_bytes(ctx->big_lds_edges));
             }
         }
 #ifdef WFSA_EXPERIMENTS
@@ -2155,8 +2182,13 @@ int enqueue_compiled(wfsa_dev* ctx, bool with_grad, bool want_logq, const unsign
         }
         if (with_grad && tables == 0)   // the blocks accumulate into their slabs
             HIP_TRY(hipMemsetAsync(ctx->gpart.ptr, 0, size_t(ctx->c_grid) * size_t(np) * sizeof(double), s));
-        if (with_grad) HIP_TRY(wfsa::launch_compiled(c, ctx->c_grid, kGradBlock, lds, s));
-        else HIP_TRY(wfsa::launch_compiled(c, ctx->i_grid, ctx->i_block, lds, s, ktimed ? ctx->k0[slot] : nullptr,
+        if (with_grad) {
+            HIP_TRY(wfsa::launch_compiled(c, ctx->c_grid, kGradBlock, lds, s));
+        } else if (dot) {
+            HIP_TRY(wfsa::launch_step_dot(c, ctx->i_grid, ctx->i_block, lds, s, ktimed ? ctx->k0[slot] : nullptr,
+                                          ktimed ? ctx->kc[slot] : nullptr));
+            ++ctx->stats.ll_dot_launches;
+        } else HIP_TRY(wfsa::launch_compiled(c, ctx->i_grid, ctx->i_block, lds, s, ktimed ? ctx->k0[slot] : nullptr,
                                            ktimed ? ctx->kc[slot] : nullptr));
     }
     if (ktimed && ctx->n_groups == 0) HIP_TRY(record(ctx, ctx->kc, slot, s));
@@ -2686,16 +2718,24 @@ int build_qw_batches(wfsa_dev* ctx) {
 // blocks one CU holds at the launch's actual LDS (the big-bubble staging
 // included) -- else the update stays a kernel of its own.
 size_t qn_launch_lds(wfsa_dev* ctx) {   // enqueue_compiled's LDS for the per-iteration launch (no log q)
+    const bool dot = ll_dot(ctx, false, false);
+    const size_t off = dot ? 0 : big_stage_off(ctx);
     if (bubbles_fused(ctx, false) && ctx->n_big > 0)
-        return big_stage_off(ctx) + size_t(ctx->i_block / kWave) * size_t(wfsa::big_stage_bytes(ctx->big_lds_edges));
-    return ctx->i_lds;
+        return off + size_t(ctx->i_block / kWave) * size_t(wfsa::big_stage_bytes(ctx->big_lds_edges));
+    return dot ? 0 : ctx->i_lds;
 }
 bool qw_resident(wfsa_dev* ctx) {
+    // the kernel and the variant the step launches: 0 fbs_kernel, else
+    // step_dot_kernel with or without the rmin column and the exchange
     const size_t lds = qn_launch_lds(ctx);
-    if (ctx->qw_res_lds != lds || ctx->qw_res_block != ctx->i_block) {
+    const bool dot = ll_dot(ctx, false, false), rmin = ctx->qn_rmin, px = ctx->comm != nullptr;
+    const int variant = dot ? 1 + (rmin ? 1 : 0) + (px ? 2 : 0) : 0;
+    if (ctx->qw_res_lds != lds || ctx->qw_res_block != ctx->i_block || ctx->qw_res_variant != variant) {
         ctx->qw_res_lds = lds;
         ctx->qw_res_block = ctx->i_block;
-        ctx->qw_res_per_cu = wfsa::fbs_qn_blocks_per_cu(ctx->i_block, lds);
+        ctx->qw_res_variant = variant;
+        ctx->qw_res_per_cu = dot ? wfsa::step_dot_blocks_per_cu(ctx->i_block, lds, rmin, px)
+                                 : wfsa::fbs_qn_blocks_per_cu(ctx->i_block, lds);
     }
     return int64_t(ctx->i_grid) <= int64_t(ctx->n_cu) * ctx->qw_res_per_cu;
 }
@@ -2912,8 +2952,11 @@ int flush_qn_finish(wfsa_dev* ctx) {
 void drop_graph(wfsa_dev* ctx) {
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
-    ctx->graph_exec = nullptr;
-    ctx->graph = nullptr;
+    if (ctx->graph_exec_nq) (void)hipGraphExecDestroy(ctx->graph_exec_nq);
+    if (ctx->graph_nq) (void)hipGraphDestroy(ctx->graph_nq);
+    ctx->graph_exec = ctx->graph_exec_nq = nullptr;
+    ctx->graph = ctx->graph_nq = nullptr;
+    ctx->graph_last = false;
     ctx->graph_failed = false;
 }
 
@@ -3028,6 +3071,7 @@ int wfsa_dev_create(int device, wfsa_dev** out) {
         ctx->qw_poll_limit = 256;
     }
     if (const char* e = std::getenv("WFSA_QN_LAST_SELF")) ctx->qw_last_self = e[0] != '0';
+    if (const char* e = std::getenv("WFSA_LL_DOT")) ctx->use_ll_dot = e[0] != '0';
 
     HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&ctx->ev0));
@@ -3390,18 +3434,23 @@ static int objective_grad_begin_impl(wfsa_dev* ctx, const double* w_full, int wa
     ctx->weights_staged = false;
     if (np > 0 && w_full) std::memcpy(win, w_full, size_t(np) * sizeof(double));
     HIP_TRY(hipEventRecord(ctx->ev0, s));
-    if (ctx->use_graph && !ctx->graph_exec && !ctx->graph_failed) {
+    // one captured sequence serves both kinds of call (it computes log q)
+    // unless the call without log q launches other kernels: then one each
+    const bool nq = ctx->use_graph && !want_logq && ll_dot(ctx, false, false);
+    hipGraphExec_t& gexec = nq ? ctx->graph_exec_nq : ctx->graph_exec;
+    hipGraph_t& graph = nq ? ctx->graph_nq : ctx->graph;
+    if (ctx->use_graph && !gexec && !ctx->graph_failed) {
         // capture once; a capture the runtime rejects falls back to eager launches
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int rc = enqueue_iteration(ctx, true);
+            const int rc = enqueue_iteration(ctx, !nq);
             hipGraph_t g = nullptr;
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (rc == WFSA_OK && e == hipSuccess && g &&
-                hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0) == hipSuccess) {
-                ctx->graph = g;
+                hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0) == hipSuccess) {
+                graph = g;
             } else {
                 if (g) (void)hipGraphDestroy(g);
-                ctx->graph_exec = nullptr;
+                gexec = nullptr;
                 ctx->graph_failed = true;
                 (void)hipGetLastError();
             }
@@ -3410,7 +3459,8 @@ static int objective_grad_begin_impl(wfsa_dev* ctx, const double* w_full, int wa
             (void)hipGetLastError();
         }
     }
-    if (ctx->graph_exec) HIP_TRY(hipGraphLaunch(ctx->graph_exec, s));
+    ctx->graph_last = gexec != nullptr;
+    if (gexec) HIP_TRY(hipGraphLaunch(gexec, s));
     else if (int rc = enqueue_iteration(ctx, want_logq != 0)) return rc;
     if (ctx->comm) {
         COMM_TRY(ctx, ctx->out.ptr, size_t(np) + 1, wfsa::RedOp::SumF64, s);
@@ -3421,7 +3471,7 @@ static int objective_grad_begin_impl(wfsa_dev* ctx, const double* w_full, int wa
     HIP_TRY(hipEventRecord(ctx->ev1, s));
     ++ctx->seq;
     ctx->in_flight = true;
-    ctx->logq_ready = want_logq != 0 || ctx->graph_exec != nullptr;
+    ctx->logq_ready = want_logq != 0 || (gexec != nullptr && !nq);
     return WFSA_OK;
 }
 

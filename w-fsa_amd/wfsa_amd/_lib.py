@@ -51,6 +51,7 @@ class DevStats(C.Structure):
         ("dense_blas", i32), ("qn_inkernel_waves", i32), ("qn_batches", i32),
         ("stream_block", i32), ("stream_w_lds", i32), ("stream_wide", i32), ("stream_multi", i32),
         ("stream_delta", i32), ("bubbles_fused", i32), ("grad_tables", i32), ("wave_lgrad", i32),
+        ("ll_dot_launches", i64),
     ]
 
 
