@@ -126,6 +126,7 @@ typedef struct {
     int32_t grad_tables;       /* the preparation-time gradient pass accumulates in LDS (0: per-block slabs in HBM) */
     int32_t wave_lgrad;        /* the traversal wave kernel's gradient table is in LDS (1) or global (0); -1: no wave kernel configured */
     int64_t ll_dot_launches;   /* step launches without the stream pass so far: the trivial words' log-likelihood as a dot product (WFSA_LL_DOT=0: none) */
+    double best_path_ms;       /* last wfsa_dev_best_paths call: device time of its kernels */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -198,6 +199,27 @@ int wfsa_dev_load_paths(wfsa_dev* ctx, int32_t n_params, int64_t n_paths, const 
  * (a (min, +) trellis over its row slots; WFSA_ERR_ARG until an evaluation
  * at real weights has run). */
 int wfsa_dev_rmin(wfsa_dev* ctx, double* rmin, int64_t* string_index);
+
+/* Viterbi decode: the most probable accepting path of every loaded string at
+ * w_full (GetWeight form, as objective_grad takes it) -- a (max, +) pass with
+ * back-pointers over the byte-step trellis, one wavefront per string,
+ * whichever tier serves the string in the learning path.
+ *   best_logw[s] = max over accepting paths of the sum of the path's weights,
+ *                  -inf when the string has none (NULL allowed);
+ *   *n_entries   = total length of the paths' parameter lists (NULL allowed).
+ * best_paths_get then copies the paths out: pidx[prow[s] .. prow[s + 1]) are
+ * the Fsa parameter ids of string s's best path in path order, repeats kept
+ * (single-member groups carry no id, as everywhere); an unrecognized string
+ * has an empty range.  Ties are broken by a fixed rule (the first in-edge of
+ * a node, the lowest end node, its first end edge), so equal weights give
+ * equal results.  Valid until the next load or best_paths call.
+ * The call is local to the rank (no collective, like logq) and touches no
+ * state of the learning path: evaluations, rmin and the QN loop continue as
+ * if it had not run.  WFSA_ERR_ARG before a model and a corpus are loaded,
+ * while an evaluation is in flight and in matrix-file mode; on the dense path
+ * WFSA_ERR_CAPACITY (no trellis is built there: load with WFSA_DENSE=0). */
+int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries);
+int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx);
 
 /* Where each loaded string runs (after compilation): tier[s] = -1 compiled
  * stream (trivial words + bubbles), 0 / 1 LDS-slab traversal, 2 wide

@@ -105,6 +105,15 @@ int wfsa_learner_get_x(wfsa_learner* l, double* x);
 int wfsa_learner_get_grad(wfsa_learner* l, double* grad);
 int wfsa_learner_set_x(wfsa_learner* l, const double* x);
 int wfsa_learner_get_p(wfsa_learner* l, double* p);                 /* [n_local_strings] */
+/* Viterbi decode at the current x (wfsa_dev_best_paths with w_full from
+ * GetWeight; after a device-resident run, the state it left): per local
+ * recognized string, in get_p's order, best_logw = the log weight of its most
+ * probable path; *n_entries = the total length of the paths' parameter lists.
+ * best_paths_get copies them out: pidx[prow[s] .. prow[s + 1]) = the Fsa
+ * parameter ids (full numbering) of string s's path in path order.  Local to
+ * the rank: no collective. */
+int wfsa_learner_best_paths(wfsa_learner* l, double* best_logw, int64_t* n_entries);
+int wfsa_learner_best_paths_get(wfsa_learner* l, int64_t* prow, int32_t* pidx);
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out);      /* [n_full]          */
 int wfsa_learner_path_counts(wfsa_learner* l, double* out, uint8_t* recognized); /* [shard size] */
 int wfsa_learner_renormalize(wfsa_learner* l);                      /* Learner::Renormalize */

@@ -567,4 +567,26 @@ const std::vector<double>& Learner::GetLogQ() {
     return logq;
 }
 
+const std::vector<double>& Learner::EvaluateLogQ() {
+    EvaluateDevice(grad_cache, true);
+    return logq;
+}
+
+void Learner::BestPaths(double* best_logw, int64_t* n_entries) {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
+    const double none = 0.0;
+    get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
+    const int rc = wfsa_dev_best_paths(dev, w_full.data(), best_logw, n_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_best_paths: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_best_paths");
+}
+
+void Learner::BestPathsGet(int64_t* prow, int32_t* pidx) const {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    const int rc = wfsa_dev_best_paths_get(dev, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_best_paths_get: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_best_paths_get");
+}
+
 }  // namespace wfsa

@@ -136,6 +136,15 @@ public:
     const std::vector<double>& GetP() const { return p; }
     const std::vector<double>& GetLastGradient() const { return grad_cache; }   // trimmed, last evaluation
     const std::vector<double>& GetLogQ();           // fetches log q from the device
+    // log q of the local recognized strings from one evaluation at the current x
+    const std::vector<double>& EvaluateLogQ();
+    // Viterbi decode at the current x (wfsa_dev_best_paths with GetWeight's
+    // w_full): per local recognized string, in p's order, the log weight of its
+    // best path; *n_entries = total length of the paths' parameter lists, which
+    // BestPathsGet copies out (prow[n_local + 1], pidx: Fsa parameter ids in
+    // path order)
+    void BestPaths(double* best_logw, int64_t* n_entries);
+    void BestPathsGet(int64_t* prow, int32_t* pidx) const;
     const std::vector<int32_t>& GetTrimmedIndex() const { return trimmed_weights; }
     const std::vector<double>& GetPathCounts() const { return path_count_local; }   // per local corpus string
     const std::vector<uint8_t>& GetRecognized() const { return recognized_local; }

@@ -414,6 +414,16 @@ int wfsa_learner_get_p(wfsa_learner* l, double* p) {
     return WFSA_OK;
 }
 
+int wfsa_learner_best_paths(wfsa_learner* l, double* best_logw, int64_t* n_entries) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->host(false).BestPaths(best_logw, n_entries); });   // (no collective: nothing to abort)
+}
+
+int wfsa_learner_best_paths_get(wfsa_learner* l, int64_t* prow, int32_t* pidx) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->base->BestPathsGet(prow, pidx); });
+}
+
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out) {
     if (!l || !out) return null_arg("learner/out");
     const auto& v = l->base->GetTrimmedIndex();

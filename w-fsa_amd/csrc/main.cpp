@@ -3,7 +3,7 @@
 // objective/gradient (and the Hessian's count covariance) on the GPU.
 //
 //   wfsa -a A.wfsa -c C.corpus [-opt Hessian|QuasiNewton] [-e epochs] [-l eta]
-//        [-tol t] [-i flags] [-n] [-eval] [-s] [-o out.wfsa] [-x] [-p] [-d device]
+//        [-tol t] [-i flags] [-n] [-eval] [-s] [-o out.wfsa] [-x] [-p] [-bp best.tsv] [-d device]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -43,13 +43,15 @@ void usage() {
                  "  -r, --recognize N      path order of -p / -m >: 0 breadth-first (default), 1 depth-first\n"
                  "  -m, --matrix <FILE|>FILE  load the path matrices FILE.{C,M,P,prob,aux} instead of -a/-c,\n"
                  "                         or save them (after -a/-c: the paths enumerated on the host)\n"
+                 "  -bp, --best-paths FILE after optimization (and -n), write per recognized string its most probable path:\n"
+                 "                         string, log weight, weight / q, Fsa parameter indices in path order (tab separated)\n"
                  "  -d, --device N         GPU to use (0)\n";
 }
 
 }  // namespace
 
 int main(int argc, const char* argv[]) {
-    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices;
+    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths;
     int epochs = 20, initflags = 0, device = 0;
     double eta = 1.0, tol = 1e-6;
     bool normalize = false, suppress = false, evaluate = false, initx = false;
@@ -75,6 +77,7 @@ int main(int argc, const char* argv[]) {
         else if (a == "-opt" || a == "--optimizer") optimizer = next();
         else if (a == "-d" || a == "--device") device = std::atoi(next());
         else if (a == "-m" || a == "--matrix" || a == "--matrices") matrices = next();
+        else if (a == "-bp" || a == "--best-paths") best_paths = next();
         else if (a == "-n" || a == "--normalize") normalize = true;
         else if (a == "-eval" || a == "--eval" || a == "--evaluate") evaluate = true;
         else if (a == "-s" || a == "--suppress") suppress = true;
@@ -102,6 +105,7 @@ int main(int argc, const char* argv[]) {
         learner.SetDevice(device);
         Fsa fsa;
         bool have_fsa = false;
+        std::vector<std::string> recognized_strings;   // -bp: the local recognized strings, in corpus order
         if (!matrices.empty() && matrices.front() == '<') {   // src/main.cpp:123-137: skip Corpus and Fsa
             std::cerr << "Loading matrices \"" << matrices.substr(1) << "\" ... ";
             if (!learner.LoadMatrices(matrices.substr(1)))
@@ -156,6 +160,14 @@ int main(int argc, const char* argv[]) {
             for (const auto& word : corpus) rec.Recognize(word.first.c_str(), Path("", fsa.GetStartState()), recognize == 0);
         }
         learner.BuildFrom(fsa, corpus);
+        if (!best_paths.empty()) {
+            const auto& rec = learner.GetRecognized();
+            size_t s = 0;
+            for (const auto& word : corpus) {
+                if (s < rec.size() && rec[s]) recognized_strings.push_back(word.first);
+                ++s;
+            }
+        }
         if (print || (!matrices.empty() && matrices.front() == '>'))   // P / M for -p and for saving
             learner.EnumeratePaths(fsa, corpus, recognize == 0);
         std::cerr << "Recognize:\n\tstrings: " << learner.GetNumberOfStrings()
@@ -216,6 +228,26 @@ int main(int argc, const char* argv[]) {
             if (learner.HaltCondition(tol)) break;
         }
         if (normalize) learner.Renormalize();
+        if (!best_paths.empty()) {   // the Viterbi decode at the final x, log q from one evaluation there
+            if (!have_fsa) throw MyError("-bp needs an automaton and a corpus (-a / -c): matrix-file mode has no trellis");
+            const size_t n = recognized_strings.size();
+            std::vector<double> logw(n);
+            int64_t n_entries = 0;
+            learner.BestPaths(logw.data(), &n_entries);
+            std::vector<int64_t> prow(n + 1);
+            std::vector<int32_t> pidx(size_t(n_entries) + 1);
+            learner.BestPathsGet(prow.data(), pidx.data());
+            const std::vector<double> logq = learner.EvaluateLogQ();
+            FILE* bf = std::fopen(best_paths.c_str(), "w");
+            if (!bf) throw MyError("Unable to open \"", best_paths, "\" for writing!");
+            for (size_t s = 0; s < n; ++s) {
+                std::fprintf(bf, "%s\t%.15g\t%.15g\t", recognized_strings[s].c_str(), logw[s], std::exp(logw[s] - logq[s]));
+                for (int64_t q = prow[s]; q < prow[s + 1]; ++q)
+                    std::fprintf(bf, q > prow[s] ? " %d" : "%d", pidx[size_t(q)]);
+                std::fputc('\n', bf);
+            }
+            std::fclose(bf);
+        }
         if (evaluate) {
             const auto results = learner.GetOptimizationResult(print);
             std::cerr.precision(15);   // DBL_DIG

@@ -38,6 +38,7 @@
 #include "matrix_path.hpp"
 #include "sym_solver.hpp"
 #include "fb_kernels.hpp"
+#include "best_path.hpp"
 #include "trellis_model.hpp"
 
 namespace {
@@ -423,6 +424,18 @@ struct wfsa_dev {
     int hft_grid = 0;
     int64_t hft_stride = 0;
     int32_t hft_vm = 0;
+
+    // Viterbi decode (wfsa_dev_best_paths, best_path.hpp): its own weights,
+    // edge log-weights, per-wave scratch, work counter and results; the last
+    // call's paths as Fsa parameter lists stay on the host for _get
+    int32_t bp_max_dst = 1;      // the most destinations of one byte (model)
+    DevBuf<double> bp_w, bp_lw, bp_score, bp_best;
+    DevBuf<int32_t> bp_back, bp_path;
+    DevBuf<unsigned> bp_ctr;
+    hipEvent_t bp_ev0 = nullptr, bp_ev1 = nullptr;
+    bool bp_valid = false;
+    std::vector<int64_t> bp_prow;
+    std::vector<int32_t> bp_pidx;
 
     // communicator
     std::unique_ptr<wfsa::Collective> comm;
@@ -3104,7 +3117,7 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     ctx->comm.reset();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->flag) (void)hipHostFree(ctx->flag);
-    for (hipEvent_t ev : {ctx->ev0, ctx->ev1})
+    for (hipEvent_t ev : {ctx->ev0, ctx->ev1, ctx->bp_ev0, ctx->bp_ev1})
         if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
@@ -3119,6 +3132,7 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
     if (int rc = check_ctx(ctx)) return rc;
     if (!model) return fail(WFSA_ERR_ARG, "null model");
     drop_graph(ctx);
+    ctx->bp_valid = false;
     ctx->slot_order.clear();   // (a QN set-up belongs to the previous model)
     ctx->slot_groups.clear();
     ctx->qn_fused = false;
@@ -3192,6 +3206,8 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
             v.shrink_to_fit();
         }
         eptr.push_back(int32_t(esrc.size()));
+        ctx->bp_max_dst = 1;
+        for (int c = 0; c < 256; ++c) ctx->bp_max_dst = std::max(ctx->bp_max_dst, cptr[size_t(c) + 1] - cptr[size_t(c)]);
         if (dst.empty()) dst.push_back(0);
         if (esrc.empty()) { esrc.push_back(0); eg.push_back(0); }
         HIP_TRY(ctx->w_cptr.upload(cptr.data(), cptr.size(), s));
@@ -3251,6 +3267,7 @@ int wfsa_dev_load_corpus(wfsa_dev* ctx, const uint8_t* sym, const int64_t* off, 
     ctx->total_sym = total;
     ctx->max_len = int32_t(max_len);
     ctx->has_corpus = true;
+    ctx->bp_valid = false;
     ctx->prep_level = 0;
     ctx->stats.n_strings = n_strings;
     ctx->stats.total_symbols = total;
@@ -3295,6 +3312,7 @@ int wfsa_dev_load_paths(wfsa_dev* ctx, int32_t n_params, int64_t n_paths, const 
         if (mcol[k] < 0 || mcol[k] >= n_paths) return fail(WFSA_ERR_ARG, "M cols != P rows");
     if (n_strings >= (int64_t(1) << 31) - 1) return fail(WFSA_ERR_ARG, "too many strings for one device");
     drop_graph(ctx);
+    ctx->bp_valid = false;
     ctx->dense.reset();
     ctx->dense_struct = false;
     hipStream_t s = ctx->stream;
@@ -4381,6 +4399,113 @@ int wfsa_dev_get_stats(wfsa_dev* ctx, wfsa_dev_stats* out) {
     out->comm_ranks = ctx->comm ? ctx->comm->nranks() : 1;
     const char* ps = ctx->comm ? ctx->comm->peer_state() : "off";
     out->comm_peer = std::strcmp(ps, "on") == 0 ? 1 : std::strcmp(ps, "failed") == 0 ? -1 : 0;
+    return WFSA_OK;
+}
+
+
+// Viterbi decode (best_path.hpp): the waves in flight come from a scratch
+// budget of 1 GiB (two score rows and the back-pointers per wave), at most 16
+// per CU and never more than there are strings -- the corpus does not size it.
+// The path's edge ids expand to Fsa parameters on the host (h_pptr / h_pidx).
+int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "best_paths: matrix-file mode has no automaton to decode over");
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "best_paths: load a model and a corpus first");
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "best_paths: an evaluation is in flight");
+    if (ctx->dense)
+        return fail(WFSA_ERR_CAPACITY, "best_paths: the dense path builds no trellis; load the model with WFSA_DENSE=0 to decode it");
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    ctx->bp_valid = false;
+    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
+    const int64_t wave_bytes = wfsa::best_path_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->bp_max_dst);
+    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
+    if (fit < 1)
+        return fail(WFSA_ERR_CAPACITY, "best_paths: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations) exceeds the budget",
+                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->bp_max_dst);
+    const int wpb = int(std::min<int64_t>(wfsa::kBestWavesPerBlock, fit));
+    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({16 * int64_t(ctx->n_cu), fit, S}));
+    const int grid = int(std::max<int64_t>(1, waves / wpb));
+    const int64_t n_waves = int64_t(grid) * wpb;
+    hipStream_t s = ctx->stream;
+    if (!ctx->bp_ev0) {
+        HIP_TRY(hipEventCreate(&ctx->bp_ev0));
+        HIP_TRY(hipEventCreate(&ctx->bp_ev1));
+    }
+    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
+    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    const size_t n_path = size_t(ctx->total_sym + S);
+    HIP_TRY(ctx->bp_w.upload(hw.data(), hw.size(), s));
+    HIP_TRY(ctx->bp_lw.alloc(size_t(E + X)));
+    HIP_TRY(ctx->bp_score.alloc(size_t(n_waves * wfsa::best_path_score_doubles(ctx->n_nodes))));
+    HIP_TRY(ctx->bp_back.alloc(size_t(n_waves * wfsa::best_path_back_ints(ctx->max_len, ctx->bp_max_dst))));
+    HIP_TRY(ctx->bp_ctr.alloc(1));
+    HIP_TRY(ctx->bp_best.alloc(size_t(S)));
+    HIP_TRY(ctx->bp_path.alloc(n_path));
+    wfsa::BestPathArgs a{};
+    a.w.c_ptr = ctx->w_cptr.ptr;
+    a.w.dst = ctx->w_dst.ptr;
+    a.w.e_ptr = ctx->w_eptr.ptr;
+    a.w.e_src = ctx->w_esrc.ptr;
+    a.w.e_g = ctx->w_eg.ptr;
+    a.x_ptr = ctx->x_ptr.ptr;
+    a.pptr = ctx->pptr.ptr;
+    a.pidx = ctx->pidx.ptr;
+    a.n_nodes = ctx->n_nodes;
+    a.start = ctx->start;
+    a.n_edges = int32_t(E);
+    a.n_end = int32_t(X);
+    a.sym = ctx->sym.ptr;
+    a.off = ctx->off.ptr;
+    a.n_strings = int32_t(S);
+    a.max_len = ctx->max_len;
+    a.max_dst = ctx->bp_max_dst;
+    a.wt = ctx->bp_w.ptr;
+    a.lw = ctx->bp_lw.ptr;
+    a.score = ctx->bp_score.ptr;
+    a.back = ctx->bp_back.ptr;
+    a.ctr = ctx->bp_ctr.ptr;
+    a.best = ctx->bp_best.ptr;
+    a.path = ctx->bp_path.ptr;
+    HIP_TRY(hipEventRecord(ctx->bp_ev0, s));
+    HIP_TRY(wfsa::launch_best_paths(a, grid, wpb, s));
+    HIP_TRY(hipEventRecord(ctx->bp_ev1, s));
+    std::vector<int32_t> path(n_path);
+    std::vector<int64_t> off(size_t(S) + 1);
+    if (best_logw && S > 0) HIP_TRY(ctx->bp_best.download(best_logw, size_t(S), s));
+    HIP_TRY(ctx->bp_path.download(path.data(), n_path, s));
+    HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->bp_ev0, ctx->bp_ev1));
+    ctx->stats.best_path_ms = double(ms);
+    // the path as Fsa parameters: the edges' parameter lists in path order
+    ctx->bp_prow.assign(size_t(S) + 1, 0);
+    ctx->bp_pidx.clear();
+    for (int64_t i = 0; i < S; ++i) {
+        const int32_t* pe = path.data() + off[i] + i;
+        const int64_t L = off[i + 1] - off[i];
+        if (pe[0] >= 0)
+            for (int64_t t = 0; t <= L; ++t) {
+                const int64_t g = pe[t];
+                if (g < 0 || g >= E + X || (t < L) != (g < E))
+                    return fail(WFSA_ERR_HIP, "best_paths: string %lld: edge %lld at step %lld is not a path edge", (long long)i,
+                                (long long)g, (long long)t);
+                ctx->bp_pidx.insert(ctx->bp_pidx.end(), ctx->h_pidx.begin() + ctx->h_pptr[size_t(g)],
+                                    ctx->h_pidx.begin() + ctx->h_pptr[size_t(g) + 1]);
+            }
+        ctx->bp_prow[size_t(i) + 1] = int64_t(ctx->bp_pidx.size());
+    }
+    ctx->bp_valid = true;
+    if (n_entries) *n_entries = int64_t(ctx->bp_pidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->bp_valid) return fail(WFSA_ERR_ARG, "best_paths_get: no wfsa_dev_best_paths result since the last load");
+    if (prow) std::memcpy(prow, ctx->bp_prow.data(), ctx->bp_prow.size() * sizeof(int64_t));
+    if (pidx && !ctx->bp_pidx.empty()) std::memcpy(pidx, ctx->bp_pidx.data(), ctx->bp_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
 

@@ -282,6 +282,19 @@ class QuasiNewtonLearner:
         check_host(load().wfsa_learner_get_p(self._h, _ptr(a)))
         return a
 
+    def BestPaths(self):
+        """Viterbi decode at the current x: (logw, prow, pidx) over the local
+        recognized strings in p()'s order -- logw[s] the log weight of string
+        s's most probable path, pidx[prow[s]:prow[s + 1]] its Fsa parameter ids
+        (full numbering) in path order"""
+        logw = np.zeros(self.info()["n_local_strings"], dtype=np.float64)
+        n = C.c_int64()
+        check_host(load().wfsa_learner_best_paths(self._h, _ptr(logw), C.byref(n)))
+        prow = np.zeros(len(logw) + 1, dtype=np.int64)
+        pidx = np.zeros(max(n.value, 1), dtype=np.int32)
+        check_host(load().wfsa_learner_best_paths_get(self._h, _ptr(prow), _ptr(pidx)))
+        return logw, prow, pidx[:n.value]
+
     def trimmed_index(self):
         a = np.zeros(self.info()["n_full"], dtype=np.int32)
         check_host(load().wfsa_learner_trimmed_index(self._h, _ptr(a)))
@@ -508,6 +521,21 @@ class Device:
         r, i = C.c_double(), C.c_int64()
         check_dev(load().wfsa_dev_rmin(self._h, C.byref(r), C.byref(i)))
         return r.value, i.value
+
+    def best_paths(self, w_full):
+        """Viterbi decode of every loaded string at w_full: (logw, prow, pidx) --
+        logw[s] the log weight of the most probable accepting path (-inf: none),
+        pidx[prow[s]:prow[s + 1]] its Fsa parameter ids in path order"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        logw = np.zeros(self.n_strings, dtype=np.float64)
+        n = C.c_int64()
+        check_dev(load().wfsa_dev_best_paths(self._h, _ptr(w), _ptr(logw), C.byref(n)))
+        prow = np.zeros(self.n_strings + 1, dtype=np.int64)
+        pidx = np.zeros(max(n.value, 1), dtype=np.int32)
+        check_dev(load().wfsa_dev_best_paths_get(self._h, _ptr(prow), _ptr(pidx)))
+        return logw, prow, pidx[:n.value]
 
     def comm_init(self, nranks, rank, unique_id):
         buf = (C.c_uint8 * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))
