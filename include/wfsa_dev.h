@@ -127,6 +127,7 @@ typedef struct {
     int32_t wave_lgrad;        /* the traversal wave kernel's gradient table is in LDS (1) or global (0); -1: no wave kernel configured */
     int64_t ll_dot_launches;   /* step launches without the stream pass so far: the trivial words' log-likelihood as a dot product (WFSA_LL_DOT=0: none) */
     double best_path_ms;       /* last wfsa_dev_best_paths call: device time of its kernels */
+    double kbest_path_ms;      /* last wfsa_dev_kbest_paths call: device time of its kernels */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -220,6 +221,36 @@ int wfsa_dev_rmin(wfsa_dev* ctx, double* rmin, int64_t* string_index);
  * WFSA_ERR_CAPACITY (no trellis is built there: load with WFSA_DENSE=0). */
 int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries);
 int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx);
+
+/* K-best decode: the k most probable accepting paths of every loaded string at
+ * w_full, 1 <= k <= WFSA_KBEST_MAX -- best_paths' trellis pass with a sorted
+ * list of k scores and k (in-edge, source rank) back-pointers per live node, a
+ * wave-wide top-k over the end edges and k back-tracks (kbest_path.hip).
+ *   *n_paths   = paths found over all strings (NULL allowed);
+ *   *n_entries = total length of their parameter lists (NULL allowed).
+ * kbest_paths_get copies them out (any pointer may be NULL): string s owns the
+ * paths srow[s] .. srow[s + 1], in descending weight; logw[t] is path t's log
+ * weight and pidx[prow[t] .. prow[t + 1]) its Fsa parameter ids in path order,
+ * repeats kept, as best_paths_get gives them.  A string with m < k accepting
+ * paths of finite weight has m paths (an unrecognized string none): a weight
+ * of -inf never enters a list.
+ * Paths are ordered by (weight descending, in-edge ascending, rank of the
+ * prefix at the source ascending) at every node, and by (weight descending,
+ * end node ascending, end edge ascending, rank ascending) at the end.  The
+ * order is total and does not depend on k, and a weight is one left-to-right
+ * sum, so the first j paths of a k result are the j result bit for bit, and
+ * the k = 1 result is best_paths' result bit for bit.
+ * Valid until the next load or kbest_paths call; a best_paths result and a
+ * kbest_paths result do not invalidate each other.  Local to the rank, and
+ * leaves the learning path untouched, as best_paths does.  Errors as for
+ * best_paths (WFSA_ERR_ARG before a model and a corpus are loaded, while an
+ * evaluation is in flight and in matrix-file mode; WFSA_ERR_CAPACITY on the
+ * dense path and when one string's scratch exceeds the budget); k outside
+ * 1 .. WFSA_KBEST_MAX is WFSA_ERR_ARG. */
+#define WFSA_KBEST_MAX 16
+int wfsa_dev_kbest_paths(wfsa_dev* ctx, const double* w_full, int32_t k, int64_t* n_paths, int64_t* n_entries);
+int wfsa_dev_kbest_paths_get(wfsa_dev* ctx, int64_t* srow /* [n_strings + 1] */, double* logw /* [n_paths] */,
+                             int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
 
 /* Where each loaded string runs (after compilation): tier[s] = -1 compiled
  * stream (trivial words + bubbles), 0 / 1 LDS-slab traversal, 2 wide

@@ -114,6 +114,19 @@ int wfsa_learner_get_p(wfsa_learner* l, double* p);                 /* [n_local_
  * the rank: no collective. */
 int wfsa_learner_best_paths(wfsa_learner* l, double* best_logw, int64_t* n_entries);
 int wfsa_learner_best_paths_get(wfsa_learner* l, int64_t* prow, int32_t* pidx);
+/* K-best decode at the current x (wfsa_dev_kbest_paths with w_full from
+ * GetWeight), 1 <= k <= WFSA_KBEST_MAX: *n_paths = the paths found over the
+ * local recognized strings, *n_entries = the total length of their parameter
+ * lists (either may be NULL).  kbest_paths_get copies them out (any pointer
+ * may be NULL): string s, in get_p's order, owns the paths srow[s] ..
+ * srow[s + 1] in descending weight (at most k; fewer when it has fewer paths
+ * of finite weight), logw[t] is path t's log weight and
+ * pidx[prow[t] .. prow[t + 1]) its Fsa parameter ids (full numbering) in path
+ * order.  The first path of every string is best_paths' path.  Local to the
+ * rank: no collective. */
+int wfsa_learner_kbest_paths(wfsa_learner* l, int32_t k, int64_t* n_paths, int64_t* n_entries);
+int wfsa_learner_kbest_paths_get(wfsa_learner* l, int64_t* srow /* [n_local_strings + 1] */, double* logw /* [n_paths] */,
+                                 int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out);      /* [n_full]          */
 int wfsa_learner_path_counts(wfsa_learner* l, double* out, uint8_t* recognized); /* [shard size] */
 int wfsa_learner_renormalize(wfsa_learner* l);                      /* Learner::Renormalize */

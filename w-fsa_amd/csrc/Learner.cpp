@@ -589,4 +589,21 @@ void Learner::BestPathsGet(int64_t* prow, int32_t* pidx) const {
     ThrowOnDevError(rc, "wfsa_dev_best_paths_get");
 }
 
+void Learner::KBestPaths(int32_t k, int64_t* n_paths, int64_t* n_entries) {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
+    const double none = 0.0;
+    get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
+    const int rc = wfsa_dev_kbest_paths(dev, w_full.data(), k, n_paths, n_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_kbest_paths: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_kbest_paths");
+}
+
+void Learner::KBestPathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    const int rc = wfsa_dev_kbest_paths_get(dev, srow, logw, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_kbest_paths_get: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_kbest_paths_get");
+}
+
 }  // namespace wfsa

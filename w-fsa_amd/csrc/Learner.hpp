@@ -145,6 +145,14 @@ public:
     // path order)
     void BestPaths(double* best_logw, int64_t* n_entries);
     void BestPathsGet(int64_t* prow, int32_t* pidx) const;
+    // K-best decode at the current x (wfsa_dev_kbest_paths with GetWeight's
+    // w_full), 1 <= k <= WFSA_KBEST_MAX: *n_paths = paths found over the local
+    // recognized strings, *n_entries = total length of their parameter lists.
+    // KBestPathsGet copies them out: string s (p's order) owns the paths
+    // srow[s] .. srow[s + 1] in descending weight, logw[t] is path t's log
+    // weight, pidx[prow[t] .. prow[t + 1]) its Fsa parameter ids in path order
+    void KBestPaths(int32_t k, int64_t* n_paths, int64_t* n_entries);
+    void KBestPathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const;
     const std::vector<int32_t>& GetTrimmedIndex() const { return trimmed_weights; }
     const std::vector<double>& GetPathCounts() const { return path_count_local; }   // per local corpus string
     const std::vector<uint8_t>& GetRecognized() const { return recognized_local; }

@@ -424,6 +424,16 @@ int wfsa_learner_best_paths_get(wfsa_learner* l, int64_t* prow, int32_t* pidx) {
     return guarded([&] { l->base->BestPathsGet(prow, pidx); });
 }
 
+int wfsa_learner_kbest_paths(wfsa_learner* l, int32_t k, int64_t* n_paths, int64_t* n_entries) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->host(false).KBestPaths(k, n_paths, n_entries); });   // (no collective: nothing to abort)
+}
+
+int wfsa_learner_kbest_paths_get(wfsa_learner* l, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->base->KBestPathsGet(srow, logw, prow, pidx); });
+}
+
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out) {
     if (!l || !out) return null_arg("learner/out");
     const auto& v = l->base->GetTrimmedIndex();

@@ -3,7 +3,8 @@
 // objective/gradient (and the Hessian's count covariance) on the GPU.
 //
 //   wfsa -a A.wfsa -c C.corpus [-opt Hessian|QuasiNewton] [-e epochs] [-l eta]
-//        [-tol t] [-i flags] [-n] [-eval] [-s] [-o out.wfsa] [-x] [-p] [-bp best.tsv] [-d device]
+//        [-tol t] [-i flags] [-n] [-eval] [-s] [-o out.wfsa] [-x] [-p] [-bp best.tsv] [-kbp K kbest.tsv]
+//        [-d device]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -45,14 +46,16 @@ void usage() {
                  "                         or save them (after -a/-c: the paths enumerated on the host)\n"
                  "  -bp, --best-paths FILE after optimization (and -n), write per recognized string its most probable path:\n"
                  "                         string, log weight, weight / q, Fsa parameter indices in path order (tab separated)\n"
+                 "  -kbp, --k-best-paths K FILE  likewise its K (1 .. 16) most probable paths, best first, one line each:\n"
+                 "                         string, rank (1 = best), log weight, weight / q, Fsa parameter indices in path order\n"
                  "  -d, --device N         GPU to use (0)\n";
 }
 
 }  // namespace
 
 int main(int argc, const char* argv[]) {
-    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths;
-    int epochs = 20, initflags = 0, device = 0;
+    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths;
+    int epochs = 20, initflags = 0, device = 0, kbest = 0;
     double eta = 1.0, tol = 1e-6;
     bool normalize = false, suppress = false, evaluate = false, initx = false;
     bool print = false, print_recognize = false;
@@ -78,6 +81,10 @@ int main(int argc, const char* argv[]) {
         else if (a == "-d" || a == "--device") device = std::atoi(next());
         else if (a == "-m" || a == "--matrix" || a == "--matrices") matrices = next();
         else if (a == "-bp" || a == "--best-paths") best_paths = next();
+        else if (a == "-kbp" || a == "--k-best-paths") {
+            kbest = std::atoi(next());
+            kbest_paths = next();
+        }
         else if (a == "-n" || a == "--normalize") normalize = true;
         else if (a == "-eval" || a == "--eval" || a == "--evaluate") evaluate = true;
         else if (a == "-s" || a == "--suppress") suppress = true;
@@ -105,7 +112,7 @@ int main(int argc, const char* argv[]) {
         learner.SetDevice(device);
         Fsa fsa;
         bool have_fsa = false;
-        std::vector<std::string> recognized_strings;   // -bp: the local recognized strings, in corpus order
+        std::vector<std::string> recognized_strings;   // -bp / -kbp: the local recognized strings, in corpus order
         if (!matrices.empty() && matrices.front() == '<') {   // src/main.cpp:123-137: skip Corpus and Fsa
             std::cerr << "Loading matrices \"" << matrices.substr(1) << "\" ... ";
             if (!learner.LoadMatrices(matrices.substr(1)))
@@ -160,7 +167,7 @@ int main(int argc, const char* argv[]) {
             for (const auto& word : corpus) rec.Recognize(word.first.c_str(), Path("", fsa.GetStartState()), recognize == 0);
         }
         learner.BuildFrom(fsa, corpus);
-        if (!best_paths.empty()) {
+        if (!best_paths.empty() || !kbest_paths.empty()) {
             const auto& rec = learner.GetRecognized();
             size_t s = 0;
             for (const auto& word : corpus) {
@@ -247,6 +254,28 @@ int main(int argc, const char* argv[]) {
                 std::fputc('\n', bf);
             }
             std::fclose(bf);
+        }
+        if (!kbest_paths.empty()) {   // the K-best decode at the final x, log q from one evaluation there
+            if (!have_fsa) throw MyError("-kbp needs an automaton and a corpus (-a / -c): matrix-file mode has no trellis");
+            const size_t n = recognized_strings.size();
+            int64_t n_paths = 0, n_entries = 0;
+            learner.KBestPaths(kbest, &n_paths, &n_entries);
+            std::vector<int64_t> srow(n + 1), prow(size_t(n_paths) + 1);
+            std::vector<double> logw(size_t(n_paths) + 1);
+            std::vector<int32_t> pidx(size_t(n_entries) + 1);
+            learner.KBestPathsGet(srow.data(), logw.data(), prow.data(), pidx.data());
+            const std::vector<double> logq = learner.EvaluateLogQ();
+            FILE* kf = std::fopen(kbest_paths.c_str(), "w");
+            if (!kf) throw MyError("Unable to open \"", kbest_paths, "\" for writing!");
+            for (size_t s = 0; s < n; ++s)
+                for (int64_t t = srow[s]; t < srow[s + 1]; ++t) {
+                    std::fprintf(kf, "%s\t%lld\t%.15g\t%.15g\t", recognized_strings[s].c_str(), (long long)(t - srow[s] + 1),
+                                 logw[size_t(t)], std::exp(logw[size_t(t)] - logq[s]));
+                    for (int64_t q = prow[size_t(t)]; q < prow[size_t(t) + 1]; ++q)
+                        std::fprintf(kf, q > prow[size_t(t)] ? " %d" : "%d", pidx[size_t(q)]);
+                    std::fputc('\n', kf);
+                }
+            std::fclose(kf);
         }
         if (evaluate) {
             const auto results = learner.GetOptimizationResult(print);

@@ -39,6 +39,7 @@
 #include "sym_solver.hpp"
 #include "fb_kernels.hpp"
 #include "best_path.hpp"
+#include "kbest_path.hpp"
 #include "trellis_model.hpp"
 
 namespace {
@@ -436,6 +437,18 @@ struct wfsa_dev {
     bool bp_valid = false;
     std::vector<int64_t> bp_prow;
     std::vector<int32_t> bp_pidx;
+
+    // K-best decode (wfsa_dev_kbest_paths, kbest_path.hpp): buffers of its own
+    // again, so a best_paths result and a kbest_paths result live side by side
+    int64_t kb_in_edges = 0;     // in-edges over all bytes (model): a back-pointer packs one with a rank
+    DevBuf<double> kb_w, kb_lw, kb_score, kb_best;
+    DevBuf<int32_t> kb_back, kb_path;
+    DevBuf<unsigned> kb_ctr;
+    hipEvent_t kb_ev0 = nullptr, kb_ev1 = nullptr;
+    bool kb_valid = false;
+    std::vector<int64_t> kb_srow, kb_prow;
+    std::vector<double> kb_logw;
+    std::vector<int32_t> kb_pidx;
 
     // communicator
     std::unique_ptr<wfsa::Collective> comm;
@@ -3117,7 +3130,7 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     ctx->comm.reset();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->flag) (void)hipHostFree(ctx->flag);
-    for (hipEvent_t ev : {ctx->ev0, ctx->ev1, ctx->bp_ev0, ctx->bp_ev1})
+    for (hipEvent_t ev : {ctx->ev0, ctx->ev1, ctx->bp_ev0, ctx->bp_ev1, ctx->kb_ev0, ctx->kb_ev1})
         if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
@@ -3133,6 +3146,7 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
     if (!model) return fail(WFSA_ERR_ARG, "null model");
     drop_graph(ctx);
     ctx->bp_valid = false;
+    ctx->kb_valid = false;
     ctx->slot_order.clear();   // (a QN set-up belongs to the previous model)
     ctx->slot_groups.clear();
     ctx->qn_fused = false;
@@ -3208,6 +3222,7 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
         eptr.push_back(int32_t(esrc.size()));
         ctx->bp_max_dst = 1;
         for (int c = 0; c < 256; ++c) ctx->bp_max_dst = std::max(ctx->bp_max_dst, cptr[size_t(c) + 1] - cptr[size_t(c)]);
+        ctx->kb_in_edges = int64_t(esrc.size());
         if (dst.empty()) dst.push_back(0);
         if (esrc.empty()) { esrc.push_back(0); eg.push_back(0); }
         HIP_TRY(ctx->w_cptr.upload(cptr.data(), cptr.size(), s));
@@ -3268,6 +3283,7 @@ int wfsa_dev_load_corpus(wfsa_dev* ctx, const uint8_t* sym, const int64_t* off, 
     ctx->max_len = int32_t(max_len);
     ctx->has_corpus = true;
     ctx->bp_valid = false;
+    ctx->kb_valid = false;
     ctx->prep_level = 0;
     ctx->stats.n_strings = n_strings;
     ctx->stats.total_symbols = total;
@@ -3313,6 +3329,7 @@ int wfsa_dev_load_paths(wfsa_dev* ctx, int32_t n_params, int64_t n_paths, const 
     if (n_strings >= (int64_t(1) << 31) - 1) return fail(WFSA_ERR_ARG, "too many strings for one device");
     drop_graph(ctx);
     ctx->bp_valid = false;
+    ctx->kb_valid = false;
     ctx->dense.reset();
     ctx->dense_struct = false;
     hipStream_t s = ctx->stream;
@@ -4508,6 +4525,134 @@ int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
     if (pidx && !ctx->bp_pidx.empty()) std::memcpy(pidx, ctx->bp_pidx.data(), ctx->bp_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
+
+// K-best decode (kbest_path.hpp): wfsa_dev_best_paths with lists of k in place
+// of scalars.  The waves in flight are sized the same way (1 GiB of scratch,
+// 16 per CU, no more than there are strings), from the scratch of one wave at
+// this k; the paths' edge ids expand to Fsa parameters on the host.
+int wfsa_dev_kbest_paths(wfsa_dev* ctx, const double* w_full, int32_t k, int64_t* n_paths, int64_t* n_entries) {
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "kbest_paths: matrix-file mode has no automaton to decode over");
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "kbest_paths: load a model and a corpus first");
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "kbest_paths: an evaluation is in flight");
+    if (k < 1 || k > WFSA_KBEST_MAX) return fail(WFSA_ERR_ARG, "kbest_paths: k = %d is outside 1 .. %d", int(k), WFSA_KBEST_MAX);
+    if (ctx->dense)
+        return fail(WFSA_ERR_CAPACITY, "kbest_paths: the dense path builds no trellis; load the model with WFSA_DENSE=0 to decode it");
+    static_assert(WFSA_KBEST_MAX == wfsa::kKBestMax, "the header's limit is the kernel's largest capacity");
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    ctx->kb_valid = false;
+    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
+    if (ctx->kb_in_edges >= wfsa::kKBestMaxEdges || X >= wfsa::kKBestMaxEdges)
+        return fail(WFSA_ERR_CAPACITY, "kbest_paths: %lld in-edges / %lld end edges do not fit a packed back-pointer (limit %lld)",
+                    (long long)ctx->kb_in_edges, (long long)X, (long long)wfsa::kKBestMaxEdges);
+    const int64_t wave_bytes = wfsa::kbest_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->bp_max_dst, k);
+    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
+    if (fit < 1)
+        return fail(WFSA_ERR_CAPACITY,
+                    "kbest_paths: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations, k = %d) exceeds the budget",
+                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->bp_max_dst, int(k));
+    const int wpb = int(std::min<int64_t>(wfsa::kKBestWavesPerBlock, fit));
+    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({16 * int64_t(ctx->n_cu), fit, S}));
+    const int grid = int(std::max<int64_t>(1, waves / wpb));
+    const int64_t n_waves = int64_t(grid) * wpb;
+    hipStream_t s = ctx->stream;
+    if (!ctx->kb_ev0) {
+        HIP_TRY(hipEventCreate(&ctx->kb_ev0));
+        HIP_TRY(hipEventCreate(&ctx->kb_ev1));
+    }
+    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
+    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    const size_t n_path = size_t(ctx->total_sym + S) * size_t(k);
+    const size_t n_best = size_t(S) * size_t(k);
+    HIP_TRY(ctx->kb_w.upload(hw.data(), hw.size(), s));
+    HIP_TRY(ctx->kb_lw.alloc(size_t(E + X)));
+    HIP_TRY(ctx->kb_score.alloc(size_t(n_waves * wfsa::kbest_score_doubles(ctx->n_nodes, k))));
+    HIP_TRY(ctx->kb_back.alloc(size_t(n_waves * wfsa::kbest_back_ints(ctx->max_len, ctx->bp_max_dst, k))));
+    HIP_TRY(ctx->kb_ctr.alloc(1));
+    HIP_TRY(ctx->kb_best.alloc(n_best));
+    HIP_TRY(ctx->kb_path.alloc(n_path));
+    wfsa::KBestArgs a{};
+    a.w.c_ptr = ctx->w_cptr.ptr;
+    a.w.dst = ctx->w_dst.ptr;
+    a.w.e_ptr = ctx->w_eptr.ptr;
+    a.w.e_src = ctx->w_esrc.ptr;
+    a.w.e_g = ctx->w_eg.ptr;
+    a.x_ptr = ctx->x_ptr.ptr;
+    a.pptr = ctx->pptr.ptr;
+    a.pidx = ctx->pidx.ptr;
+    a.n_nodes = ctx->n_nodes;
+    a.start = ctx->start;
+    a.n_edges = int32_t(E);
+    a.n_end = int32_t(X);
+    a.sym = ctx->sym.ptr;
+    a.off = ctx->off.ptr;
+    a.n_strings = int32_t(S);
+    a.max_len = ctx->max_len;
+    a.max_dst = ctx->bp_max_dst;
+    a.k = k;
+    a.wt = ctx->kb_w.ptr;
+    a.lw = ctx->kb_lw.ptr;
+    a.score = ctx->kb_score.ptr;
+    a.back = ctx->kb_back.ptr;
+    a.ctr = ctx->kb_ctr.ptr;
+    a.best = ctx->kb_best.ptr;
+    a.path = ctx->kb_path.ptr;
+    HIP_TRY(hipEventRecord(ctx->kb_ev0, s));
+    HIP_TRY(wfsa::launch_kbest_paths(a, grid, wpb, s));
+    HIP_TRY(hipEventRecord(ctx->kb_ev1, s));
+    std::vector<int32_t> path(n_path);
+    std::vector<double> best(n_best);
+    std::vector<int64_t> off(size_t(S) + 1);
+    HIP_TRY(ctx->kb_best.download(best.data(), n_best, s));
+    HIP_TRY(ctx->kb_path.download(path.data(), n_path, s));
+    HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->kb_ev0, ctx->kb_ev1));
+    ctx->stats.kbest_path_ms = double(ms);
+    // the paths as Fsa parameters: the edges' parameter lists in path order;
+    // a string's finite weights come first, descending
+    ctx->kb_srow.assign(size_t(S) + 1, 0);
+    ctx->kb_prow.assign(1, 0);
+    ctx->kb_logw.clear();
+    ctx->kb_pidx.clear();
+    for (int64_t i = 0; i < S; ++i) {
+        const int64_t L = off[i + 1] - off[i];
+        const int32_t* ps = path.data() + (off[i] + i) * int64_t(k);
+        for (int32_t t = 0; t < k; ++t) {
+            const double v = best[size_t(i) * size_t(k) + size_t(t)];
+            if (!(v > -INFINITY)) break;
+            const int32_t* pe = ps + int64_t(t) * (L + 1);
+            for (int64_t j = 0; j <= L; ++j) {
+                const int64_t g = pe[j];
+                if (g < 0 || g >= E + X || (j < L) != (g < E))
+                    return fail(WFSA_ERR_HIP, "kbest_paths: string %lld, path %d: edge %lld at step %lld is not a path edge", (long long)i,
+                                int(t), (long long)g, (long long)j);
+                ctx->kb_pidx.insert(ctx->kb_pidx.end(), ctx->h_pidx.begin() + ctx->h_pptr[size_t(g)],
+                                    ctx->h_pidx.begin() + ctx->h_pptr[size_t(g) + 1]);
+            }
+            ctx->kb_logw.push_back(v);
+            ctx->kb_prow.push_back(int64_t(ctx->kb_pidx.size()));
+        }
+        ctx->kb_srow[size_t(i) + 1] = int64_t(ctx->kb_logw.size());
+    }
+    ctx->kb_valid = true;
+    if (n_paths) *n_paths = int64_t(ctx->kb_logw.size());
+    if (n_entries) *n_entries = int64_t(ctx->kb_pidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_kbest_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->kb_valid) return fail(WFSA_ERR_ARG, "kbest_paths_get: no wfsa_dev_kbest_paths result since the last load");
+    if (srow) std::memcpy(srow, ctx->kb_srow.data(), ctx->kb_srow.size() * sizeof(int64_t));
+    if (logw && !ctx->kb_logw.empty()) std::memcpy(logw, ctx->kb_logw.data(), ctx->kb_logw.size() * sizeof(double));
+    if (prow) std::memcpy(prow, ctx->kb_prow.data(), ctx->kb_prow.size() * sizeof(int64_t));
+    if (pidx && !ctx->kb_pidx.empty()) std::memcpy(pidx, ctx->kb_pidx.data(), ctx->kb_pidx.size() * sizeof(int32_t));
+    return WFSA_OK;
+}
+
 
 
 // Entry points that take part in rank collectives: a failure on this rank

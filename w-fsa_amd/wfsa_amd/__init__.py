@@ -295,6 +295,21 @@ class QuasiNewtonLearner:
         check_host(load().wfsa_learner_best_paths_get(self._h, _ptr(prow), _ptr(pidx)))
         return logw, prow, pidx[:n.value]
 
+    def KBestPaths(self, k):
+        """K-best decode at the current x: (srow, logw, prow, pidx) over the
+        local recognized strings in p()'s order -- string s owns the paths
+        srow[s]:srow[s + 1] in descending weight (at most k), logw[t] is path
+        t's log weight, pidx[prow[t]:prow[t + 1]] its Fsa parameter ids (full
+        numbering) in path order"""
+        n_paths, n = C.c_int64(), C.c_int64()
+        check_host(load().wfsa_learner_kbest_paths(self._h, int(k), C.byref(n_paths), C.byref(n)))
+        srow = np.zeros(self.info()["n_local_strings"] + 1, dtype=np.int64)
+        logw = np.zeros(max(n_paths.value, 1), dtype=np.float64)
+        prow = np.zeros(n_paths.value + 1, dtype=np.int64)
+        pidx = np.zeros(max(n.value, 1), dtype=np.int32)
+        check_host(load().wfsa_learner_kbest_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
+        return srow, logw[:n_paths.value], prow, pidx[:n.value]
+
     def trimmed_index(self):
         a = np.zeros(self.info()["n_full"], dtype=np.int32)
         check_host(load().wfsa_learner_trimmed_index(self._h, _ptr(a)))
@@ -536,6 +551,24 @@ class Device:
         pidx = np.zeros(max(n.value, 1), dtype=np.int32)
         check_dev(load().wfsa_dev_best_paths_get(self._h, _ptr(prow), _ptr(pidx)))
         return logw, prow, pidx[:n.value]
+
+    def kbest_paths(self, w_full, k):
+        """K-best decode of every loaded string at w_full, 1 <= k <= 16:
+        (srow, logw, prow, pidx) -- string s owns the paths srow[s]:srow[s + 1]
+        in descending weight (at most k; none when it has no accepting path of
+        finite weight), logw[t] is path t's log weight,
+        pidx[prow[t]:prow[t + 1]] its Fsa parameter ids in path order"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        n_paths, n = C.c_int64(), C.c_int64()
+        check_dev(load().wfsa_dev_kbest_paths(self._h, _ptr(w), int(k), C.byref(n_paths), C.byref(n)))
+        srow = np.zeros(self.n_strings + 1, dtype=np.int64)
+        logw = np.zeros(max(n_paths.value, 1), dtype=np.float64)
+        prow = np.zeros(n_paths.value + 1, dtype=np.int64)
+        pidx = np.zeros(max(n.value, 1), dtype=np.int32)
+        check_dev(load().wfsa_dev_kbest_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
+        return srow, logw[:n_paths.value], prow, pidx[:n.value]
 
     def comm_init(self, nranks, rank, unique_id):
         buf = (C.c_uint8 * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))

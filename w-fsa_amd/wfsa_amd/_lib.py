@@ -51,7 +51,7 @@ class DevStats(C.Structure):
         ("dense_blas", i32), ("qn_inkernel_waves", i32), ("qn_batches", i32),
         ("stream_block", i32), ("stream_w_lds", i32), ("stream_wide", i32), ("stream_multi", i32),
         ("stream_delta", i32), ("bubbles_fused", i32), ("grad_tables", i32), ("wave_lgrad", i32),
-        ("ll_dot_launches", i64), ("best_path_ms", dbl),
+        ("ll_dot_launches", i64), ("best_path_ms", dbl), ("kbest_path_ms", dbl),
     ]
 
 
@@ -82,6 +82,8 @@ _SIGS = {
     "wfsa_dev_rmin": (C.c_int, [vp, vp, vp]),
     "wfsa_dev_best_paths": (C.c_int, [vp, vp, vp, P(i64)]),
     "wfsa_dev_best_paths_get": (C.c_int, [vp, vp, vp]),
+    "wfsa_dev_kbest_paths": (C.c_int, [vp, vp, C.c_int32, P(i64), P(i64)]),
+    "wfsa_dev_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_sym_factor": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp]),
     "wfsa_dev_sym_solve": (C.c_int, [vp, vp]),
     "wfsa_dev_sym_factor_coo": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -141,6 +143,8 @@ _SIGS = {
     "wfsa_learner_get_p": (C.c_int, [vp, vp]),
     "wfsa_learner_best_paths": (C.c_int, [vp, vp, P(i64)]),
     "wfsa_learner_best_paths_get": (C.c_int, [vp, vp, vp]),
+    "wfsa_learner_kbest_paths": (C.c_int, [vp, C.c_int32, P(i64), P(i64)]),
+    "wfsa_learner_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_learner_trimmed_index": (C.c_int, [vp, vp]),
     "wfsa_learner_path_counts": (C.c_int, [vp, vp, vp]),
     "wfsa_learner_renormalize": (C.c_int, [vp]),
