@@ -38,8 +38,7 @@
 #include "matrix_path.hpp"
 #include "sym_solver.hpp"
 #include "fb_kernels.hpp"
-#include "best_path.hpp"
-#include "kbest_path.hpp"
+#include "decode.hpp"
 #include "trellis_model.hpp"
 
 namespace {
@@ -119,6 +118,17 @@ constexpr int kQnDepth = 8;   // device-resident QN steps in flight
 
 // weights after the results in the host-mapped buffer, 16-byte aligned
 inline size_t weights_off(int32_t np) { return (size_t(np) + 3) & ~size_t(1); }
+
+// what one decode entry point keeps on the device (decode.hpp): its own
+// weights, edge log-weights, per-wave scratch, work counter and results, and
+// the events that time its kernels
+struct DecodeBufs {
+    DevBuf<double> w, lw, score, best;
+    DevBuf<int32_t> back, path;
+    DevBuf<unsigned> ctr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool valid = false;   // the host holds a result of this entry point for _get
+};
 
 }  // namespace
 
@@ -426,26 +436,15 @@ struct wfsa_dev {
     int64_t hft_stride = 0;
     int32_t hft_vm = 0;
 
-    // Viterbi decode (wfsa_dev_best_paths, best_path.hpp): its own weights,
-    // edge log-weights, per-wave scratch, work counter and results; the last
-    // call's paths as Fsa parameter lists stay on the host for _get
-    int32_t bp_max_dst = 1;      // the most destinations of one byte (model)
-    DevBuf<double> bp_w, bp_lw, bp_score, bp_best;
-    DevBuf<int32_t> bp_back, bp_path;
-    DevBuf<unsigned> bp_ctr;
-    hipEvent_t bp_ev0 = nullptr, bp_ev1 = nullptr;
-    bool bp_valid = false;
+    // The decodes (wfsa_dev_best_paths, wfsa_dev_kbest_paths; decode.hpp).
+    // Each entry point has buffers of its own, so a best_paths result and a
+    // kbest_paths result live side by side; the last call's paths as Fsa
+    // parameter lists stay on the host for _get
+    int32_t max_dst = 1;         // the most destinations of one byte (model)
+    int64_t n_in_edges = 0;      // in-edges over all bytes (model): a K-best back-pointer packs one with a rank
+    DecodeBufs bp, kb;
     std::vector<int64_t> bp_prow;
     std::vector<int32_t> bp_pidx;
-
-    // K-best decode (wfsa_dev_kbest_paths, kbest_path.hpp): buffers of its own
-    // again, so a best_paths result and a kbest_paths result live side by side
-    int64_t kb_in_edges = 0;     // in-edges over all bytes (model): a back-pointer packs one with a rank
-    DevBuf<double> kb_w, kb_lw, kb_score, kb_best;
-    DevBuf<int32_t> kb_back, kb_path;
-    DevBuf<unsigned> kb_ctr;
-    hipEvent_t kb_ev0 = nullptr, kb_ev1 = nullptr;
-    bool kb_valid = false;
     std::vector<int64_t> kb_srow, kb_prow;
     std::vector<double> kb_logw;
     std::vector<int32_t> kb_pidx;
@@ -2986,6 +2985,9 @@ void drop_graph(wfsa_dev* ctx) {
     ctx->graph_failed = false;
 }
 
+// a load ends the decode results held for _get
+void invalidate_decodes(wfsa_dev* ctx) { ctx->bp.valid = ctx->kb.valid = false; }
+
 // weights in / results out, sized by n_params
 int alloc_param_buffers(wfsa_dev* ctx) {
     HIP_TRY(ctx->w_full.alloc(size_t(ctx->n_params) + 2));
@@ -3130,8 +3132,11 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     ctx->comm.reset();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->flag) (void)hipHostFree(ctx->flag);
-    for (hipEvent_t ev : {ctx->ev0, ctx->ev1, ctx->bp_ev0, ctx->bp_ev1, ctx->kb_ev0, ctx->kb_ev1})
+    for (hipEvent_t ev : {ctx->ev0, ctx->ev1})
         if (ev) (void)hipEventDestroy(ev);
+    for (DecodeBufs* d : {&ctx->bp, &ctx->kb})
+        for (hipEvent_t ev : {d->ev0, d->ev1})
+            if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
             if (ev) (void)hipEventDestroy(ev);
@@ -3145,8 +3150,7 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
     if (int rc = check_ctx(ctx)) return rc;
     if (!model) return fail(WFSA_ERR_ARG, "null model");
     drop_graph(ctx);
-    ctx->bp_valid = false;
-    ctx->kb_valid = false;
+    invalidate_decodes(ctx);
     ctx->slot_order.clear();   // (a QN set-up belongs to the previous model)
     ctx->slot_groups.clear();
     ctx->qn_fused = false;
@@ -3220,9 +3224,9 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
             v.shrink_to_fit();
         }
         eptr.push_back(int32_t(esrc.size()));
-        ctx->bp_max_dst = 1;
-        for (int c = 0; c < 256; ++c) ctx->bp_max_dst = std::max(ctx->bp_max_dst, cptr[size_t(c) + 1] - cptr[size_t(c)]);
-        ctx->kb_in_edges = int64_t(esrc.size());
+        ctx->max_dst = 1;
+        for (int c = 0; c < 256; ++c) ctx->max_dst = std::max(ctx->max_dst, cptr[size_t(c) + 1] - cptr[size_t(c)]);
+        ctx->n_in_edges = int64_t(esrc.size());
         if (dst.empty()) dst.push_back(0);
         if (esrc.empty()) { esrc.push_back(0); eg.push_back(0); }
         HIP_TRY(ctx->w_cptr.upload(cptr.data(), cptr.size(), s));
@@ -3282,8 +3286,7 @@ int wfsa_dev_load_corpus(wfsa_dev* ctx, const uint8_t* sym, const int64_t* off, 
     ctx->total_sym = total;
     ctx->max_len = int32_t(max_len);
     ctx->has_corpus = true;
-    ctx->bp_valid = false;
-    ctx->kb_valid = false;
+    invalidate_decodes(ctx);
     ctx->prep_level = 0;
     ctx->stats.n_strings = n_strings;
     ctx->stats.total_symbols = total;
@@ -3328,8 +3331,7 @@ int wfsa_dev_load_paths(wfsa_dev* ctx, int32_t n_params, int64_t n_paths, const 
         if (mcol[k] < 0 || mcol[k] >= n_paths) return fail(WFSA_ERR_ARG, "M cols != P rows");
     if (n_strings >= (int64_t(1) << 31) - 1) return fail(WFSA_ERR_ARG, "too many strings for one device");
     drop_graph(ctx);
-    ctx->bp_valid = false;
-    ctx->kb_valid = false;
+    invalidate_decodes(ctx);
     ctx->dense.reset();
     ctx->dense_struct = false;
     hipStream_t s = ctx->stream;
@@ -4420,46 +4422,59 @@ int wfsa_dev_get_stats(wfsa_dev* ctx, wfsa_dev_stats* out) {
 }
 
 
-// Viterbi decode (best_path.hpp): the waves in flight come from a scratch
-// budget of 1 GiB (two score rows and the back-pointers per wave), at most 16
-// per CU and never more than there are strings -- the corpus does not size it.
-// The path's edge ids expand to Fsa parameters on the host (h_pptr / h_pidx).
-int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries) {
-    if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "best_paths: matrix-file mode has no automaton to decode over");
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "best_paths: load a model and a corpus first");
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "best_paths: an evaluation is in flight");
+// The host side of both decodes (decode.hpp).  The waves in flight come from a
+// scratch budget of 1 GiB (two score rows and the back-pointers per wave, at
+// list length k), at most 16 per CU and never more than there are strings --
+// the corpus does not size it.  `kbest` picks the K-best kernels (also at
+// k = 1) and the checks that belong to them; `name` prefixes every message.
+// Hands back the device's raw results, in DecodeArgs' layout: best[S][k],
+// path and the strings' offsets off[S + 1]; the kernels' time goes to *ms_out.
+// The checks run in the order each entry point always had them, which is why
+// the K-best ones sit here behind `kbest` and not in front of the call.
+static int decode_run(wfsa_dev* ctx, DecodeBufs& d, const char* name, const double* w_full, int32_t k, bool kbest, double* ms_out,
+                      std::vector<double>& best, std::vector<int32_t>& path, std::vector<int64_t>& off) {
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to decode over", name);
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (kbest && (k < 1 || k > WFSA_KBEST_MAX)) return fail(WFSA_ERR_ARG, "%s: k = %d is outside 1 .. %d", name, int(k), WFSA_KBEST_MAX);
     if (ctx->dense)
-        return fail(WFSA_ERR_CAPACITY, "best_paths: the dense path builds no trellis; load the model with WFSA_DENSE=0 to decode it");
+        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to decode it", name);
     const int32_t np = ctx->n_params;
     if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    ctx->bp_valid = false;
+    d.valid = false;
     const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
-    const int64_t wave_bytes = wfsa::best_path_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->bp_max_dst);
+    if (kbest && (ctx->n_in_edges >= wfsa::kKBestMaxEdges || X >= wfsa::kKBestMaxEdges))
+        return fail(WFSA_ERR_CAPACITY, "%s: %lld in-edges / %lld end edges do not fit a packed back-pointer (limit %lld)", name,
+                    (long long)ctx->n_in_edges, (long long)X, (long long)wfsa::kKBestMaxEdges);
+    const int64_t wave_bytes = wfsa::decode_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst, k);
     const int64_t fit = (int64_t(1) << 30) / wave_bytes;
-    if (fit < 1)
-        return fail(WFSA_ERR_CAPACITY, "best_paths: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations) exceeds the budget",
-                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->bp_max_dst);
-    const int wpb = int(std::min<int64_t>(wfsa::kBestWavesPerBlock, fit));
+    if (fit < 1) {
+        char with_k[32] = "";
+        if (kbest) std::snprintf(with_k, sizeof with_k, ", k = %d", int(k));
+        return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations%s) exceeds the budget", name,
+                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst, with_k);
+    }
+    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
     const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({16 * int64_t(ctx->n_cu), fit, S}));
     const int grid = int(std::max<int64_t>(1, waves / wpb));
     const int64_t n_waves = int64_t(grid) * wpb;
     hipStream_t s = ctx->stream;
-    if (!ctx->bp_ev0) {
-        HIP_TRY(hipEventCreate(&ctx->bp_ev0));
-        HIP_TRY(hipEventCreate(&ctx->bp_ev1));
+    if (!d.ev0) {
+        HIP_TRY(hipEventCreate(&d.ev0));
+        HIP_TRY(hipEventCreate(&d.ev1));
     }
     std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
     if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
-    const size_t n_path = size_t(ctx->total_sym + S);
-    HIP_TRY(ctx->bp_w.upload(hw.data(), hw.size(), s));
-    HIP_TRY(ctx->bp_lw.alloc(size_t(E + X)));
-    HIP_TRY(ctx->bp_score.alloc(size_t(n_waves * wfsa::best_path_score_doubles(ctx->n_nodes))));
-    HIP_TRY(ctx->bp_back.alloc(size_t(n_waves * wfsa::best_path_back_ints(ctx->max_len, ctx->bp_max_dst))));
-    HIP_TRY(ctx->bp_ctr.alloc(1));
-    HIP_TRY(ctx->bp_best.alloc(size_t(S)));
-    HIP_TRY(ctx->bp_path.alloc(n_path));
-    wfsa::BestPathArgs a{};
+    const size_t n_path = size_t(ctx->total_sym + S) * size_t(k);
+    const size_t n_best = size_t(S) * size_t(k);
+    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
+    HIP_TRY(d.lw.alloc(size_t(E + X)));
+    HIP_TRY(d.score.alloc(size_t(n_waves * wfsa::decode_score_doubles(ctx->n_nodes, k))));
+    HIP_TRY(d.back.alloc(size_t(n_waves * wfsa::decode_back_ints(ctx->max_len, ctx->max_dst, k))));
+    HIP_TRY(d.ctr.alloc(1));
+    HIP_TRY(d.best.alloc(n_best));
+    HIP_TRY(d.path.alloc(n_path));
+    wfsa::DecodeArgs a{};
     a.w.c_ptr = ctx->w_cptr.ptr;
     a.w.dst = ctx->w_dst.ptr;
     a.w.e_ptr = ctx->w_eptr.ptr;
@@ -4476,143 +4491,91 @@ int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, 
     a.off = ctx->off.ptr;
     a.n_strings = int32_t(S);
     a.max_len = ctx->max_len;
-    a.max_dst = ctx->bp_max_dst;
-    a.wt = ctx->bp_w.ptr;
-    a.lw = ctx->bp_lw.ptr;
-    a.score = ctx->bp_score.ptr;
-    a.back = ctx->bp_back.ptr;
-    a.ctr = ctx->bp_ctr.ptr;
-    a.best = ctx->bp_best.ptr;
-    a.path = ctx->bp_path.ptr;
-    HIP_TRY(hipEventRecord(ctx->bp_ev0, s));
-    HIP_TRY(wfsa::launch_best_paths(a, grid, wpb, s));
-    HIP_TRY(hipEventRecord(ctx->bp_ev1, s));
-    std::vector<int32_t> path(n_path);
-    std::vector<int64_t> off(size_t(S) + 1);
-    if (best_logw && S > 0) HIP_TRY(ctx->bp_best.download(best_logw, size_t(S), s));
-    HIP_TRY(ctx->bp_path.download(path.data(), n_path, s));
+    a.max_dst = ctx->max_dst;
+    a.k = k;
+    a.wt = d.w.ptr;
+    a.lw = d.lw.ptr;
+    a.score = d.score.ptr;
+    a.back = d.back.ptr;
+    a.ctr = d.ctr.ptr;
+    a.best = d.best.ptr;
+    a.path = d.path.ptr;
+    HIP_TRY(hipEventRecord(d.ev0, s));
+    HIP_TRY(kbest ? wfsa::launch_kbest_paths(a, grid, wpb, s) : wfsa::launch_best_paths(a, grid, wpb, s));
+    HIP_TRY(hipEventRecord(d.ev1, s));
+    path.resize(n_path);
+    best.resize(n_best);
+    off.resize(size_t(S) + 1);
+    HIP_TRY(d.best.download(best.data(), n_best, s));
+    HIP_TRY(d.path.download(path.data(), n_path, s));
     HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->bp_ev0, ctx->bp_ev1));
-    ctx->stats.best_path_ms = double(ms);
-    // the path as Fsa parameters: the edges' parameter lists in path order
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    *ms_out = double(ms);
+    return WFSA_OK;
+}
+
+// One path as Fsa parameters: the parameter lists of its L + 1 combined edge
+// ids (h_pptr / h_pidx), in path order, appended to pidx.  The first L are
+// byte-consuming edges and the last is an end edge; `rank` < 0: a Viterbi path.
+static int expand_path(wfsa_dev* ctx, const char* name, int64_t string, int rank, const int32_t* pe, int64_t L,
+                       std::vector<int32_t>& pidx) {
+    const int64_t E = ctx->n_edges, X = ctx->n_end;
+    for (int64_t t = 0; t <= L; ++t) {
+        const int64_t g = pe[t];
+        if (g < 0 || g >= E + X || (t < L) != (g < E)) {
+            if (rank < 0)
+                return fail(WFSA_ERR_HIP, "%s: string %lld: edge %lld at step %lld is not a path edge", name, (long long)string, (long long)g,
+                            (long long)t);
+            return fail(WFSA_ERR_HIP, "%s: string %lld, path %d: edge %lld at step %lld is not a path edge", name, (long long)string, rank,
+                        (long long)g, (long long)t);
+        }
+        pidx.insert(pidx.end(), ctx->h_pidx.begin() + ctx->h_pptr[size_t(g)], ctx->h_pidx.begin() + ctx->h_pptr[size_t(g) + 1]);
+    }
+    return WFSA_OK;
+}
+
+// Viterbi decode: the scalar kernel at k = 1
+int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries) {
+    std::vector<double> best;
+    std::vector<int32_t> path;
+    std::vector<int64_t> off;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = decode_run(ctx, ctx->bp, "best_paths", w_full, 1, false, &ctx->stats.best_path_ms, best, path, off)) return rc;
+    const int64_t S = ctx->n_strings;
+    if (best_logw && S > 0) std::memcpy(best_logw, best.data(), size_t(S) * sizeof(double));
     ctx->bp_prow.assign(size_t(S) + 1, 0);
     ctx->bp_pidx.clear();
     for (int64_t i = 0; i < S; ++i) {
         const int32_t* pe = path.data() + off[i] + i;
-        const int64_t L = off[i + 1] - off[i];
         if (pe[0] >= 0)
-            for (int64_t t = 0; t <= L; ++t) {
-                const int64_t g = pe[t];
-                if (g < 0 || g >= E + X || (t < L) != (g < E))
-                    return fail(WFSA_ERR_HIP, "best_paths: string %lld: edge %lld at step %lld is not a path edge", (long long)i,
-                                (long long)g, (long long)t);
-                ctx->bp_pidx.insert(ctx->bp_pidx.end(), ctx->h_pidx.begin() + ctx->h_pptr[size_t(g)],
-                                    ctx->h_pidx.begin() + ctx->h_pptr[size_t(g) + 1]);
-            }
+            if (int rc = expand_path(ctx, "best_paths", i, -1, pe, off[i + 1] - off[i], ctx->bp_pidx)) return rc;
         ctx->bp_prow[size_t(i) + 1] = int64_t(ctx->bp_pidx.size());
     }
-    ctx->bp_valid = true;
+    ctx->bp.valid = true;
     if (n_entries) *n_entries = int64_t(ctx->bp_pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->bp_valid) return fail(WFSA_ERR_ARG, "best_paths_get: no wfsa_dev_best_paths result since the last load");
+    if (!ctx->bp.valid) return fail(WFSA_ERR_ARG, "best_paths_get: no wfsa_dev_best_paths result since the last load");
     if (prow) std::memcpy(prow, ctx->bp_prow.data(), ctx->bp_prow.size() * sizeof(int64_t));
     if (pidx && !ctx->bp_pidx.empty()) std::memcpy(pidx, ctx->bp_pidx.data(), ctx->bp_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
 
-// K-best decode (kbest_path.hpp): wfsa_dev_best_paths with lists of k in place
-// of scalars.  The waves in flight are sized the same way (1 GiB of scratch,
-// 16 per CU, no more than there are strings), from the scratch of one wave at
-// this k; the paths' edge ids expand to Fsa parameters on the host.
+// K-best decode: the kernel of capacity kbest_capacity(k).  A string's finite
+// weights come first, descending.
 int wfsa_dev_kbest_paths(wfsa_dev* ctx, const double* w_full, int32_t k, int64_t* n_paths, int64_t* n_entries) {
-    if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "kbest_paths: matrix-file mode has no automaton to decode over");
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "kbest_paths: load a model and a corpus first");
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "kbest_paths: an evaluation is in flight");
-    if (k < 1 || k > WFSA_KBEST_MAX) return fail(WFSA_ERR_ARG, "kbest_paths: k = %d is outside 1 .. %d", int(k), WFSA_KBEST_MAX);
-    if (ctx->dense)
-        return fail(WFSA_ERR_CAPACITY, "kbest_paths: the dense path builds no trellis; load the model with WFSA_DENSE=0 to decode it");
     static_assert(WFSA_KBEST_MAX == wfsa::kKBestMax, "the header's limit is the kernel's largest capacity");
-    const int32_t np = ctx->n_params;
-    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    ctx->kb_valid = false;
-    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
-    if (ctx->kb_in_edges >= wfsa::kKBestMaxEdges || X >= wfsa::kKBestMaxEdges)
-        return fail(WFSA_ERR_CAPACITY, "kbest_paths: %lld in-edges / %lld end edges do not fit a packed back-pointer (limit %lld)",
-                    (long long)ctx->kb_in_edges, (long long)X, (long long)wfsa::kKBestMaxEdges);
-    const int64_t wave_bytes = wfsa::kbest_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->bp_max_dst, k);
-    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
-    if (fit < 1)
-        return fail(WFSA_ERR_CAPACITY,
-                    "kbest_paths: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations, k = %d) exceeds the budget",
-                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->bp_max_dst, int(k));
-    const int wpb = int(std::min<int64_t>(wfsa::kKBestWavesPerBlock, fit));
-    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({16 * int64_t(ctx->n_cu), fit, S}));
-    const int grid = int(std::max<int64_t>(1, waves / wpb));
-    const int64_t n_waves = int64_t(grid) * wpb;
-    hipStream_t s = ctx->stream;
-    if (!ctx->kb_ev0) {
-        HIP_TRY(hipEventCreate(&ctx->kb_ev0));
-        HIP_TRY(hipEventCreate(&ctx->kb_ev1));
-    }
-    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
-    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
-    const size_t n_path = size_t(ctx->total_sym + S) * size_t(k);
-    const size_t n_best = size_t(S) * size_t(k);
-    HIP_TRY(ctx->kb_w.upload(hw.data(), hw.size(), s));
-    HIP_TRY(ctx->kb_lw.alloc(size_t(E + X)));
-    HIP_TRY(ctx->kb_score.alloc(size_t(n_waves * wfsa::kbest_score_doubles(ctx->n_nodes, k))));
-    HIP_TRY(ctx->kb_back.alloc(size_t(n_waves * wfsa::kbest_back_ints(ctx->max_len, ctx->bp_max_dst, k))));
-    HIP_TRY(ctx->kb_ctr.alloc(1));
-    HIP_TRY(ctx->kb_best.alloc(n_best));
-    HIP_TRY(ctx->kb_path.alloc(n_path));
-    wfsa::KBestArgs a{};
-    a.w.c_ptr = ctx->w_cptr.ptr;
-    a.w.dst = ctx->w_dst.ptr;
-    a.w.e_ptr = ctx->w_eptr.ptr;
-    a.w.e_src = ctx->w_esrc.ptr;
-    a.w.e_g = ctx->w_eg.ptr;
-    a.x_ptr = ctx->x_ptr.ptr;
-    a.pptr = ctx->pptr.ptr;
-    a.pidx = ctx->pidx.ptr;
-    a.n_nodes = ctx->n_nodes;
-    a.start = ctx->start;
-    a.n_edges = int32_t(E);
-    a.n_end = int32_t(X);
-    a.sym = ctx->sym.ptr;
-    a.off = ctx->off.ptr;
-    a.n_strings = int32_t(S);
-    a.max_len = ctx->max_len;
-    a.max_dst = ctx->bp_max_dst;
-    a.k = k;
-    a.wt = ctx->kb_w.ptr;
-    a.lw = ctx->kb_lw.ptr;
-    a.score = ctx->kb_score.ptr;
-    a.back = ctx->kb_back.ptr;
-    a.ctr = ctx->kb_ctr.ptr;
-    a.best = ctx->kb_best.ptr;
-    a.path = ctx->kb_path.ptr;
-    HIP_TRY(hipEventRecord(ctx->kb_ev0, s));
-    HIP_TRY(wfsa::launch_kbest_paths(a, grid, wpb, s));
-    HIP_TRY(hipEventRecord(ctx->kb_ev1, s));
-    std::vector<int32_t> path(n_path);
-    std::vector<double> best(n_best);
-    std::vector<int64_t> off(size_t(S) + 1);
-    HIP_TRY(ctx->kb_best.download(best.data(), n_best, s));
-    HIP_TRY(ctx->kb_path.download(path.data(), n_path, s));
-    HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->kb_ev0, ctx->kb_ev1));
-    ctx->stats.kbest_path_ms = double(ms);
-    // the paths as Fsa parameters: the edges' parameter lists in path order;
-    // a string's finite weights come first, descending
+    std::vector<double> best;
+    std::vector<int32_t> path;
+    std::vector<int64_t> off;
+    if (int rc = check_ctx(ctx)) return rc;
+    if (int rc = decode_run(ctx, ctx->kb, "kbest_paths", w_full, k, true, &ctx->stats.kbest_path_ms, best, path, off)) return rc;
+    const int64_t S = ctx->n_strings;
     ctx->kb_srow.assign(size_t(S) + 1, 0);
     ctx->kb_prow.assign(1, 0);
     ctx->kb_logw.clear();
@@ -4623,21 +4586,13 @@ int wfsa_dev_kbest_paths(wfsa_dev* ctx, const double* w_full, int32_t k, int64_t
         for (int32_t t = 0; t < k; ++t) {
             const double v = best[size_t(i) * size_t(k) + size_t(t)];
             if (!(v > -INFINITY)) break;
-            const int32_t* pe = ps + int64_t(t) * (L + 1);
-            for (int64_t j = 0; j <= L; ++j) {
-                const int64_t g = pe[j];
-                if (g < 0 || g >= E + X || (j < L) != (g < E))
-                    return fail(WFSA_ERR_HIP, "kbest_paths: string %lld, path %d: edge %lld at step %lld is not a path edge", (long long)i,
-                                int(t), (long long)g, (long long)j);
-                ctx->kb_pidx.insert(ctx->kb_pidx.end(), ctx->h_pidx.begin() + ctx->h_pptr[size_t(g)],
-                                    ctx->h_pidx.begin() + ctx->h_pptr[size_t(g) + 1]);
-            }
+            if (int rc = expand_path(ctx, "kbest_paths", i, int(t), ps + int64_t(t) * (L + 1), L, ctx->kb_pidx)) return rc;
             ctx->kb_logw.push_back(v);
             ctx->kb_prow.push_back(int64_t(ctx->kb_pidx.size()));
         }
         ctx->kb_srow[size_t(i) + 1] = int64_t(ctx->kb_logw.size());
     }
-    ctx->kb_valid = true;
+    ctx->kb.valid = true;
     if (n_paths) *n_paths = int64_t(ctx->kb_logw.size());
     if (n_entries) *n_entries = int64_t(ctx->kb_pidx.size());
     return WFSA_OK;
@@ -4645,7 +4600,7 @@ int wfsa_dev_kbest_paths(wfsa_dev* ctx, const double* w_full, int32_t k, int64_t
 
 int wfsa_dev_kbest_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->kb_valid) return fail(WFSA_ERR_ARG, "kbest_paths_get: no wfsa_dev_kbest_paths result since the last load");
+    if (!ctx->kb.valid) return fail(WFSA_ERR_ARG, "kbest_paths_get: no wfsa_dev_kbest_paths result since the last load");
     if (srow) std::memcpy(srow, ctx->kb_srow.data(), ctx->kb_srow.size() * sizeof(int64_t));
     if (logw && !ctx->kb_logw.empty()) std::memcpy(logw, ctx->kb_logw.data(), ctx->kb_logw.size() * sizeof(double));
     if (prow) std::memcpy(prow, ctx->kb_prow.data(), ctx->kb_prow.size() * sizeof(int64_t));
