@@ -178,7 +178,8 @@ int wfsa_dev_sym_factor_coo(wfsa_dev* ctx, int64_t n, int64_t nnz, const int32_t
  * -m "<file"): instead of an automaton and strings, the path matrices the
  * reference's BuildPaths builds.  P: n_paths x n_params CSR (prow[n_paths+1],
  * pcol/pdata[prow[n_paths]], parameter counts); M: n_strings x n_paths CSR
- * of ones (mrow[n_strings+1], mcol = path indices); p[n_strings].  Replaces
+ * of ones (mrow[n_strings+1], mcol = path indices); p[n_strings].  M names
+ * every path exactly once (a path of two strings or of none: WFSA_ERR_ARG).  Replaces
  * any loaded model and corpus; objective_grad then takes w_full = x
  * (n_params values, no trimming) and computes the reference's SpMV chain
  * (logq = log M exp(P x), grad = -P^T (rpp (.) M^T p)); recognize reports

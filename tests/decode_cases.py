@@ -61,7 +61,7 @@ def _reference(text, sym, off, wt):
     from oracle.hessian import HessianOracle
     o = Oracle.from_arrays(text, sym, off, wt)
     h = HessianOracle(o)
-    return dict(text=text, sym=sym, off=off, wt=wt, o=o, P=h.P, mrow=np.asarray(h.mrow),
+    return dict(text=text, sym=sym, off=off, wt=wt, o=o, h=h, P=h.P, mrow=np.asarray(h.mrow),
                 rec=np.flatnonzero(o.path_counts() > 0), trim=o.trimmed_index())
 
 

@@ -3329,6 +3329,21 @@ int wfsa_dev_load_paths(wfsa_dev* ctx, int32_t n_params, int64_t n_paths, const 
         if (mrow[i + 1] < mrow[i]) return fail(WFSA_ERR_ARG, "M rows not ascending at %lld", (long long)i);
     for (int64_t k = 0; k < mrow[n_strings]; ++k)
         if (mcol[k] < 0 || mcol[k] >= n_paths) return fail(WFSA_ERR_ARG, "M cols != P rows");
+    // M names every path exactly once: a path of two strings would be
+    // rewritten by one lane of mp_string_kernel while another still reads it,
+    // a path of none would keep its log weight as its gradient coefficient
+    if (mrow[n_strings] != n_paths)
+        return fail(WFSA_ERR_ARG, "M names %lld paths, P has %lld: every path belongs to exactly one string",
+                    (long long)mrow[n_strings], (long long)n_paths);
+    {
+        std::vector<uint8_t> named(size_t(n_paths), 0);
+        for (int64_t k = 0; k < mrow[n_strings]; ++k) {
+            if (named[size_t(mcol[k])])
+                return fail(WFSA_ERR_ARG, "M names path %lld twice: every path belongs to exactly one string",
+                            (long long)mcol[k]);
+            named[size_t(mcol[k])] = 1;
+        }
+    }
     if (n_strings >= (int64_t(1) << 31) - 1) return fail(WFSA_ERR_ARG, "too many strings for one device");
     drop_graph(ctx);
     invalidate_decodes(ctx);
@@ -4101,8 +4116,8 @@ static int hf_setup_impl(wfsa_dev* ctx, int64_t* n_pairs) {
     // exact min / max counts over each string's trellis (hf_trav_kernel)
     std::vector<int4> tl;
     std::vector<int32_t> tv;
-    int64_t bad_string = -1;
-    size_t bad_v = 0;
+    int64_t bad_string = -1, bad_trav_string = -1;
+    size_t bad_v = 0, bad_trav_edge = 0;   // a traversal string's edge with more than 8 equivocal parameters
     if (nfall > 0) {
         std::vector<int64_t> off(size_t(ctx->n_strings) + 1);
         HIP_TRY(ctx->off.download(off.data(), off.size(), s));
@@ -4123,6 +4138,33 @@ static int hf_setup_impl(wfsa_dev* ctx, int64_t* n_pairs) {
             if (V.empty()) continue;
             tl.push_back(make_int4(int32_t(i), int32_t(tv.size()), int32_t(V.size()), 0));
             tv.insert(tv.end(), V.begin(), V.end());
+        }
+        // hf_trav_kernel's hf_local collects at most 8 equivocal parameters of
+        // one combined edge (an epsilon chain folds into its edge and can carry
+        // more): walk the long edges as it does, and refuse the first string
+        // that would lose one.  Every long edge of the automaton is walked,
+        // whether or not it lies on the string's trellis: an edge elsewhere
+        // that shares more than 8 of the string's equivocal parameters
+        // refuses it too, which errs on the safe side
+        std::vector<int32_t> long_edges;
+        for (size_t g = 0; g + 1 < ctx->h_pptr.size(); ++g)
+            if (ctx->h_pptr[g + 1] - ctx->h_pptr[g] > 8) long_edges.push_back(int32_t(g));
+        for (size_t t = 0; t < tl.size() && !long_edges.empty() && bad_string < 0 && bad_trav_edge == 0; ++t) {
+            const int32_t* Vb = tv.data() + tl[t].y;
+            const int32_t* Ve = Vb + tl[t].z;
+            for (int32_t g : long_edges) {
+                std::vector<int32_t> seen;
+                for (int32_t q = ctx->h_pptr[size_t(g)]; q < ctx->h_pptr[size_t(g) + 1] && bad_trav_edge == 0; ++q) {
+                    const int32_t j = ctx->h_pidx[size_t(q)];
+                    if (!std::binary_search(Vb, Ve, j)) continue;
+                    if (seen.size() == 8) bad_trav_edge = size_t(ctx->h_pptr[size_t(g) + 1] - ctx->h_pptr[size_t(g)]);
+                    else if (std::find(seen.begin(), seen.end(), j) == seen.end()) seen.push_back(j);
+                }
+                if (bad_trav_edge) {
+                    bad_trav_string = tl[t].x;
+                    break;
+                }
+            }
         }
     }
     const int32_t np = ctx->n_params, nb = ctx->n_bubbles;
@@ -4165,7 +4207,7 @@ static int hf_setup_impl(wfsa_dev* ctx, int64_t* n_pairs) {
     }
     // every limit is checked before the status all-reduce below, so a rank
     // that fails never leaves the others waiting in a later collective
-    const bool local_bad = bad_string >= 0 || bad_edge_params > 0;
+    const bool local_bad = bad_string >= 0 || bad_edge_params > 0 || bad_trav_edge > 0;
     if (ctx->comm) {   // every rank learns whether any cannot build its part (no rank is left in a collective)
         DevBuf<double> t;
         double bad = local_bad ? 1.0 : 0.0;
@@ -4179,6 +4221,9 @@ static int hf_setup_impl(wfsa_dev* ctx, int64_t* n_pairs) {
     if (bad_edge_params > 0)
         return fail(WFSA_ERR_CAPACITY, "second-order terms: a bubble edge carries %zu parameters (max 8)",
                     bad_edge_params);
+    if (bad_trav_edge > 0)
+        return fail(WFSA_ERR_CAPACITY, "second-order terms: an edge of traversal string %lld carries %zu parameters, "
+                    "more than 8 of them equivocal (max 8)", (long long)bad_trav_string, bad_trav_edge);
     if (local_bad)
         return fail(WFSA_ERR_CAPACITY, "second-order terms: string %lld has %s equivocal parameters (at most %d, "
                     "from at most 4096 parameters on its paths)", (long long)bad_string,
