@@ -128,6 +128,7 @@ typedef struct {
     int64_t ll_dot_launches;   /* step launches without the stream pass so far: the trivial words' log-likelihood as a dot product (WFSA_LL_DOT=0: none) */
     double best_path_ms;       /* last wfsa_dev_best_paths call: device time of its kernels */
     double kbest_path_ms;      /* last wfsa_dev_kbest_paths call: device time of its kernels */
+    double sample_path_ms;     /* last wfsa_dev_sample_paths call: device time of its kernels */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -252,6 +253,60 @@ int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx);
 int wfsa_dev_kbest_paths(wfsa_dev* ctx, const double* w_full, int32_t k, int64_t* n_paths, int64_t* n_entries);
 int wfsa_dev_kbest_paths_get(wfsa_dev* ctx, int64_t* srow /* [n_strings + 1] */, double* logw /* [n_paths] */,
                              int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
+
+/* Posterior path sampling: n independent draws per loaded string from
+ * P(path | string) = exp(w(path)) / q_s at w_full, 1 <= n <= WFSA_SAMPLE_MAX --
+ * best_paths' trellis walk with log-sum-exp in place of max: a forward pass in
+ * the log domain whose rows are kept per position (so a q_s below the double
+ * range loses nothing), then n walks back from the end, each choosing its end
+ * edge and then its in-edge per position by inverse CDF (sample.hip).
+ *   logq[s]    = log q_s from that forward pass, -inf when the string has no
+ *                accepting path of finite weight (NULL allowed);
+ *   *n_paths   = samples over all strings (NULL allowed);
+ *   *n_entries = total length of their parameter lists (NULL allowed).
+ * sample_paths_get copies them out in kbest_paths_get's layout (any pointer may
+ * be NULL): string s owns the paths srow[s] .. srow[s + 1], logw[t] is path t's
+ * log weight and pidx[prow[t] .. prow[t + 1]) its Fsa parameter ids in path
+ * order, repeats kept.  A string with an accepting path of finite weight owns
+ * exactly n paths, in sample-index order (sample 0 first), unsorted, duplicates
+ * possible; any other string owns none.  An edge of weight -inf, or a prefix of
+ * mass 0, is never taken.  logw[t] is formed as the decoders form it (one
+ * left-to-right sum of decode_edge_weight_kernel's edge log-weights): a sampled
+ * path carries bit for bit the weight kbest_paths reports for it, and
+ * exp(logw[t] - logq[s]) is the posterior mass of that path.
+ *
+ * Reproducibility.  The random numbers are Philox4x32-10 (multipliers
+ * 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with key
+ * (lo32(seed), hi32(seed)) and counter (lo32(s), hi32(s), t, d): s the string's
+ * index among the loaded strings, t the sample index, d = 0 the choice of the
+ * end edge and d = m (1 .. L) the choice of the in-edge into position
+ * L + 1 - m.  One draw per choice: u = (((x0 << 32) | x1) >> 11) * 2^-53 from
+ * output words 0 and 1.  A choice among candidates of masses a_i >= 0 takes the
+ * first i whose running sum exceeds u * total (total: the sum in the same
+ * order); if rounding leaves none, the last candidate of positive mass.  In-edges are candidates in e_ptr order, end
+ * edges in (live slot, end edge) order, the decoders' tie order.  Hence two
+ * calls with the same weights, n and seed return the same bytes; the first j
+ * samples of every string in an n result are the j result byte for byte (a draw
+ * depends neither on n nor on which wave or lane made it); to continue a sample
+ * set, call again with another seed.
+ *
+ * Valid until the next load or sample_paths call; best_paths, kbest_paths and
+ * sample_paths results do not invalidate each other.  Local to the rank (no
+ * collective), and leaves the learning path untouched, as the decoders do.
+ * WFSA_ERR_ARG for n outside 1 .. WFSA_SAMPLE_MAX, before a model and a corpus
+ * are loaded, while an evaluation is in flight, in matrix-file mode, and from
+ * _get without a result since the last load; WFSA_ERR_CAPACITY on the dense
+ * path (load with WFSA_DENSE=0) and when one wave's scratch exceeds the 1 GiB
+ * budget. */
+#define WFSA_SAMPLE_MAX 64
+int wfsa_dev_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, uint64_t seed,
+                          double* logq /* [n_strings], NULL allowed */, int64_t* n_paths, int64_t* n_entries /* NULL allowed */);
+int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow /* [n_strings + 1] */, double* logw /* [n_paths] */,
+                              int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
+/* Test entry: the device's generator without an automaton, out[d] = the uniform
+ * of draw d = 0 .. n_draws - 1 of sample `sample` of string `string` under
+ * `seed` (the counter and key above). */
+int wfsa_dev_sample_uniforms(int device, uint64_t seed, int64_t string, int32_t sample, int32_t n_draws, double* out);
 
 /* Where each loaded string runs (after compilation): tier[s] = -1 compiled
  * stream (trivial words + bubbles), 0 / 1 LDS-slab traversal, 2 wide

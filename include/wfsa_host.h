@@ -127,6 +127,17 @@ int wfsa_learner_best_paths_get(wfsa_learner* l, int64_t* prow, int32_t* pidx);
 int wfsa_learner_kbest_paths(wfsa_learner* l, int32_t k, int64_t* n_paths, int64_t* n_entries);
 int wfsa_learner_kbest_paths_get(wfsa_learner* l, int64_t* srow /* [n_local_strings + 1] */, double* logw /* [n_paths] */,
                                  int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
+/* Posterior path sampling at the current x (wfsa_dev_sample_paths with w_full
+ * from GetWeight), 1 <= n <= WFSA_SAMPLE_MAX: n independent draws from
+ * P(path | string) per local recognized string, reproducible from `seed` as
+ * wfsa_dev.h states; logq (NULL allowed) = log q of each string from the same
+ * pass.  sample_paths_get copies them out in kbest_paths_get's layout: string
+ * s, in get_p's order, owns the n paths srow[s] .. srow[s + 1] in sample order.
+ * Local to the rank: no collective. */
+int wfsa_learner_sample_paths(wfsa_learner* l, int32_t n, uint64_t seed, double* logq /* [n_local_strings] */,
+                              int64_t* n_paths, int64_t* n_entries);
+int wfsa_learner_sample_paths_get(wfsa_learner* l, int64_t* srow /* [n_local_strings + 1] */, double* logw /* [n_paths] */,
+                                  int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out);      /* [n_full]          */
 int wfsa_learner_path_counts(wfsa_learner* l, double* out, uint8_t* recognized); /* [shard size] */
 int wfsa_learner_renormalize(wfsa_learner* l);                      /* Learner::Renormalize */

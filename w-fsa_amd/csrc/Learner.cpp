@@ -606,4 +606,21 @@ void Learner::KBestPathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t*
     ThrowOnDevError(rc, "wfsa_dev_kbest_paths_get");
 }
 
+void Learner::SamplePaths(int32_t n, uint64_t seed, double* logq, int64_t* n_paths, int64_t* n_entries) {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
+    const double none = 0.0;
+    get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
+    const int rc = wfsa_dev_sample_paths(dev, w_full.data(), n, seed, logq, n_paths, n_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_sample_paths: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_sample_paths");
+}
+
+void Learner::SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    const int rc = wfsa_dev_sample_paths_get(dev, srow, logw, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_sample_paths_get: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_sample_paths_get");
+}
+
 }  // namespace wfsa

@@ -153,6 +153,13 @@ public:
     // weight, pidx[prow[t] .. prow[t + 1]) its Fsa parameter ids in path order
     void KBestPaths(int32_t k, int64_t* n_paths, int64_t* n_entries);
     void KBestPathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const;
+    // Posterior path sampling at the current x (wfsa_dev_sample_paths with
+    // GetWeight's w_full), 1 <= n <= WFSA_SAMPLE_MAX: n independent draws per
+    // local recognized string; logq (nullable) = log q of each from the same
+    // pass.  SamplePathsGet copies them out in KBestPathsGet's layout, a
+    // string's n paths in sample order
+    void SamplePaths(int32_t n, uint64_t seed, double* logq, int64_t* n_paths, int64_t* n_entries);
+    void SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const;
     const std::vector<int32_t>& GetTrimmedIndex() const { return trimmed_weights; }
     const std::vector<double>& GetPathCounts() const { return path_count_local; }   // per local corpus string
     const std::vector<uint8_t>& GetRecognized() const { return recognized_local; }

@@ -110,5 +110,8 @@ inline int64_t decode_wave_bytes(int32_t max_len, int32_t n_nodes, int32_t max_d
 // wave's must stay below 1 GiB (the K-best kernel indexes it with 32 bits).
 hipError_t launch_best_paths(const DecodeArgs& a, int grid, int waves, hipStream_t stream);
 hipError_t launch_kbest_paths(const DecodeArgs& a, int grid, int waves, hipStream_t stream);
+// what both start with, and the sampler (sample.hpp) too: the work counter at
+// zero and decode_edge_weight_kernel's a.lw from a.wt
+hipError_t launch_edge_weights(const DecodeArgs& a, hipStream_t stream);
 
 }  // namespace wfsa

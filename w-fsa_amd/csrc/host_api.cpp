@@ -434,6 +434,16 @@ int wfsa_learner_kbest_paths_get(wfsa_learner* l, int64_t* srow, double* logw, i
     return guarded([&] { l->base->KBestPathsGet(srow, logw, prow, pidx); });
 }
 
+int wfsa_learner_sample_paths(wfsa_learner* l, int32_t n, uint64_t seed, double* logq, int64_t* n_paths, int64_t* n_entries) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->host(false).SamplePaths(n, seed, logq, n_paths, n_entries); });   // (no collective: nothing to abort)
+}
+
+int wfsa_learner_sample_paths_get(wfsa_learner* l, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->base->SamplePathsGet(srow, logw, prow, pidx); });
+}
+
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out) {
     if (!l || !out) return null_arg("learner/out");
     const auto& v = l->base->GetTrimmedIndex();

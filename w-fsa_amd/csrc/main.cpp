@@ -4,7 +4,7 @@
 //
 //   wfsa -a A.wfsa -c C.corpus [-opt Hessian|QuasiNewton] [-e epochs] [-l eta]
 //        [-tol t] [-i flags] [-n] [-eval] [-s] [-o out.wfsa] [-x] [-p] [-bp best.tsv] [-kbp K kbest.tsv]
-//        [-d device]
+//        [-sp N samples.tsv [--sample-seed S]] [-d device]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -48,14 +48,18 @@ void usage() {
                  "                         string, log weight, weight / q, Fsa parameter indices in path order (tab separated)\n"
                  "  -kbp, --k-best-paths K FILE  likewise its K (1 .. 16) most probable paths, best first, one line each:\n"
                  "                         string, rank (1 = best), log weight, weight / q, Fsa parameter indices in path order\n"
+                 "  -sp, --sample-paths N FILE  likewise N (1 .. 64) paths drawn at random from its posterior, one line each:\n"
+                 "                         string, sample index (0 first), log weight, weight / q, Fsa parameter indices in path order\n"
+                 "  --sample-seed S        seed of -sp's random numbers (0); the same seed gives the same file\n"
                  "  -d, --device N         GPU to use (0)\n";
 }
 
 }  // namespace
 
 int main(int argc, const char* argv[]) {
-    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths;
-    int epochs = 20, initflags = 0, device = 0, kbest = 0;
+    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths, sample_paths;
+    int epochs = 20, initflags = 0, device = 0, kbest = 0, n_samples = 0;
+    unsigned long long sample_seed = 0;
     double eta = 1.0, tol = 1e-6;
     bool normalize = false, suppress = false, evaluate = false, initx = false;
     bool print = false, print_recognize = false;
@@ -85,6 +89,11 @@ int main(int argc, const char* argv[]) {
             kbest = std::atoi(next());
             kbest_paths = next();
         }
+        else if (a == "-sp" || a == "--sample-paths") {
+            n_samples = std::atoi(next());
+            sample_paths = next();
+        }
+        else if (a == "--sample-seed") sample_seed = std::strtoull(next(), nullptr, 10);
         else if (a == "-n" || a == "--normalize") normalize = true;
         else if (a == "-eval" || a == "--eval" || a == "--evaluate") evaluate = true;
         else if (a == "-s" || a == "--suppress") suppress = true;
@@ -112,7 +121,7 @@ int main(int argc, const char* argv[]) {
         learner.SetDevice(device);
         Fsa fsa;
         bool have_fsa = false;
-        std::vector<std::string> recognized_strings;   // -bp / -kbp: the local recognized strings, in corpus order
+        std::vector<std::string> recognized_strings;   // -bp / -kbp / -sp: the local recognized strings, in corpus order
         if (!matrices.empty() && matrices.front() == '<') {   // src/main.cpp:123-137: skip Corpus and Fsa
             std::cerr << "Loading matrices \"" << matrices.substr(1) << "\" ... ";
             if (!learner.LoadMatrices(matrices.substr(1)))
@@ -167,7 +176,7 @@ int main(int argc, const char* argv[]) {
             for (const auto& word : corpus) rec.Recognize(word.first.c_str(), Path("", fsa.GetStartState()), recognize == 0);
         }
         learner.BuildFrom(fsa, corpus);
-        if (!best_paths.empty() || !kbest_paths.empty()) {
+        if (!best_paths.empty() || !kbest_paths.empty() || !sample_paths.empty()) {
             const auto& rec = learner.GetRecognized();
             size_t s = 0;
             for (const auto& word : corpus) {
@@ -276,6 +285,28 @@ int main(int argc, const char* argv[]) {
                     std::fputc('\n', kf);
                 }
             std::fclose(kf);
+        }
+        if (!sample_paths.empty()) {   // posterior samples at the final x, log q from the same call
+            if (!have_fsa) throw MyError("-sp needs an automaton and a corpus (-a / -c): matrix-file mode has no trellis");
+            const size_t n = recognized_strings.size();
+            int64_t n_paths = 0, n_entries = 0;
+            std::vector<double> logq(n + 1);
+            learner.SamplePaths(n_samples, sample_seed, logq.data(), &n_paths, &n_entries);
+            std::vector<int64_t> srow(n + 1), prow(size_t(n_paths) + 1);
+            std::vector<double> logw(size_t(n_paths) + 1);
+            std::vector<int32_t> pidx(size_t(n_entries) + 1);
+            learner.SamplePathsGet(srow.data(), logw.data(), prow.data(), pidx.data());
+            FILE* sf = std::fopen(sample_paths.c_str(), "w");
+            if (!sf) throw MyError("Unable to open \"", sample_paths, "\" for writing!");
+            for (size_t s = 0; s < n; ++s)
+                for (int64_t t = srow[s]; t < srow[s + 1]; ++t) {
+                    std::fprintf(sf, "%s\t%lld\t%.15g\t%.15g\t", recognized_strings[s].c_str(), (long long)(t - srow[s]),
+                                 logw[size_t(t)], std::exp(logw[size_t(t)] - logq[s]));
+                    for (int64_t q = prow[size_t(t)]; q < prow[size_t(t) + 1]; ++q)
+                        std::fprintf(sf, q > prow[size_t(t)] ? " %d" : "%d", pidx[size_t(q)]);
+                    std::fputc('\n', sf);
+                }
+            std::fclose(sf);
         }
         if (evaluate) {
             const auto results = learner.GetOptimizationResult(print);

@@ -39,6 +39,7 @@
 #include "sym_solver.hpp"
 #include "fb_kernels.hpp"
 #include "decode.hpp"
+#include "sample.hpp"
 #include "trellis_model.hpp"
 
 namespace {
@@ -443,6 +444,14 @@ struct wfsa_dev {
     int32_t max_dst = 1;         // the most destinations of one byte (model)
     int64_t n_in_edges = 0;      // in-edges over all bytes (model): a K-best back-pointer packs one with a rank
     DecodeBufs bp, kb;
+    // The sampler (wfsa_dev_sample_paths; sample.hpp): a third buffer set, plus
+    // what the forward pass keeps beside it -- the stored rows and log q -- and
+    // its last result for _get, in kbest_paths_get's layout
+    DecodeBufs sp;
+    DevBuf<double> sp_hist, sp_logq;
+    std::vector<int64_t> sp_srow, sp_prow;
+    std::vector<double> sp_logw;
+    std::vector<int32_t> sp_pidx;
     std::vector<int64_t> bp_prow;
     std::vector<int32_t> bp_pidx;
     std::vector<int64_t> kb_srow, kb_prow;
@@ -2986,7 +2995,7 @@ void drop_graph(wfsa_dev* ctx) {
 }
 
 // a load ends the decode results held for _get
-void invalidate_decodes(wfsa_dev* ctx) { ctx->bp.valid = ctx->kb.valid = false; }
+void invalidate_decodes(wfsa_dev* ctx) { ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = false; }
 
 // weights in / results out, sized by n_params
 int alloc_param_buffers(wfsa_dev* ctx) {
@@ -3134,7 +3143,7 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     if (ctx->flag) (void)hipHostFree(ctx->flag);
     for (hipEvent_t ev : {ctx->ev0, ctx->ev1})
         if (ev) (void)hipEventDestroy(ev);
-    for (DecodeBufs* d : {&ctx->bp, &ctx->kb})
+    for (DecodeBufs* d : {&ctx->bp, &ctx->kb, &ctx->sp})
         for (hipEvent_t ev : {d->ev0, d->ev1})
             if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
@@ -4653,6 +4662,140 @@ int wfsa_dev_kbest_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t
     return WFSA_OK;
 }
 
+// Posterior path sampling (sample.hpp): n draws per string, the decoders'
+// checks, waves in flight and buffers of its own (the context's `sp`).  A
+// string of positive mass owns exactly n paths, in sample order.
+int wfsa_dev_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, uint64_t seed, double* logq, int64_t* n_paths,
+                          int64_t* n_entries) {
+    static_assert(WFSA_SAMPLE_MAX == wfsa::kSampleMax, "the header's limit is one walking lane per sample");
+    const char* name = "sample_paths";
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to sample over", name);
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (n < 1 || n > WFSA_SAMPLE_MAX) return fail(WFSA_ERR_ARG, "%s: n = %d is outside 1 .. %d", name, int(n), WFSA_SAMPLE_MAX);
+    if (ctx->dense)
+        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to sample it", name);
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    DecodeBufs& d = ctx->sp;
+    d.valid = false;
+    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
+    const int64_t wave_bytes = wfsa::sample_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst);
+    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
+    if (fit < 1)
+        return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations) exceeds the budget", name,
+                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst);
+    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
+    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({16 * int64_t(ctx->n_cu), fit, S}));
+    const int grid = int(std::max<int64_t>(1, waves / wpb));
+    const int64_t n_waves = int64_t(grid) * wpb;
+    hipStream_t s = ctx->stream;
+    if (!d.ev0) {
+        HIP_TRY(hipEventCreate(&d.ev0));
+        HIP_TRY(hipEventCreate(&d.ev1));
+    }
+    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
+    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    const size_t n_path = size_t(ctx->total_sym + S) * size_t(n);
+    const size_t n_best = size_t(S) * size_t(n);
+    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
+    HIP_TRY(d.lw.alloc(size_t(E + X)));
+    HIP_TRY(d.score.alloc(size_t(n_waves * wfsa::sample_score_doubles(ctx->n_nodes))));
+    HIP_TRY(ctx->sp_hist.alloc(size_t(n_waves * wfsa::sample_hist_doubles(ctx->max_len, ctx->max_dst))));
+    HIP_TRY(d.ctr.alloc(1));
+    HIP_TRY(d.best.alloc(n_best));
+    HIP_TRY(d.path.alloc(n_path));
+    HIP_TRY(ctx->sp_logq.alloc(size_t(S)));
+    wfsa::SampleArgs a{};
+    a.d.w.c_ptr = ctx->w_cptr.ptr;
+    a.d.w.dst = ctx->w_dst.ptr;
+    a.d.w.e_ptr = ctx->w_eptr.ptr;
+    a.d.w.e_src = ctx->w_esrc.ptr;
+    a.d.w.e_g = ctx->w_eg.ptr;
+    a.d.x_ptr = ctx->x_ptr.ptr;
+    a.d.pptr = ctx->pptr.ptr;
+    a.d.pidx = ctx->pidx.ptr;
+    a.d.n_nodes = ctx->n_nodes;
+    a.d.start = ctx->start;
+    a.d.n_edges = int32_t(E);
+    a.d.n_end = int32_t(X);
+    a.d.sym = ctx->sym.ptr;
+    a.d.off = ctx->off.ptr;
+    a.d.n_strings = int32_t(S);
+    a.d.max_len = ctx->max_len;
+    a.d.max_dst = ctx->max_dst;
+    a.d.k = n;
+    a.d.wt = d.w.ptr;
+    a.d.lw = d.lw.ptr;
+    a.d.score = d.score.ptr;
+    a.d.back = nullptr;   // (no back-pointers: the rows are kept instead)
+    a.d.ctr = d.ctr.ptr;
+    a.d.best = d.best.ptr;
+    a.d.path = d.path.ptr;
+    a.hist = ctx->sp_hist.ptr;
+    a.logq = ctx->sp_logq.ptr;
+    a.seed = seed;
+    HIP_TRY(hipEventRecord(d.ev0, s));
+    HIP_TRY(wfsa::launch_sample_paths(a, grid, wpb, s));
+    HIP_TRY(hipEventRecord(d.ev1, s));
+    std::vector<int32_t> path(n_path);
+    std::vector<double> best(n_best), lq(size_t(S), 0.0);
+    std::vector<int64_t> off(size_t(S) + 1);
+    HIP_TRY(d.best.download(best.data(), n_best, s));
+    HIP_TRY(d.path.download(path.data(), n_path, s));
+    HIP_TRY(ctx->sp_logq.download(lq.data(), size_t(S), s));
+    HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    ctx->stats.sample_path_ms = double(ms);
+    ctx->sp_srow.assign(size_t(S) + 1, 0);
+    ctx->sp_prow.assign(1, 0);
+    ctx->sp_logw.clear();
+    ctx->sp_pidx.clear();
+    for (int64_t i = 0; i < S; ++i) {
+        const int64_t L = off[i + 1] - off[i];
+        const int32_t* ps = path.data() + (off[i] + i) * int64_t(n);
+        if (lq[size_t(i)] > -INFINITY)
+            for (int32_t t = 0; t < n; ++t) {
+                const double v = best[size_t(i) * size_t(n) + size_t(t)];
+                if (ps[int64_t(t) * (L + 1)] < 0 || !(v > -INFINITY))
+                    return fail(WFSA_ERR_HIP, "%s: string %lld, sample %d: the walk found no edge of positive mass", name, (long long)i, int(t));
+                if (int rc = expand_path(ctx, name, i, int(t), ps + int64_t(t) * (L + 1), L, ctx->sp_pidx)) return rc;
+                ctx->sp_logw.push_back(v);
+                ctx->sp_prow.push_back(int64_t(ctx->sp_pidx.size()));
+            }
+        ctx->sp_srow[size_t(i) + 1] = int64_t(ctx->sp_logw.size());
+    }
+    d.valid = true;
+    if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
+    if (n_paths) *n_paths = int64_t(ctx->sp_logw.size());
+    if (n_entries) *n_entries = int64_t(ctx->sp_pidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->sp.valid) return fail(WFSA_ERR_ARG, "sample_paths_get: no wfsa_dev_sample_paths result since the last load");
+    if (srow) std::memcpy(srow, ctx->sp_srow.data(), ctx->sp_srow.size() * sizeof(int64_t));
+    if (logw && !ctx->sp_logw.empty()) std::memcpy(logw, ctx->sp_logw.data(), ctx->sp_logw.size() * sizeof(double));
+    if (prow) std::memcpy(prow, ctx->sp_prow.data(), ctx->sp_prow.size() * sizeof(int64_t));
+    if (pidx && !ctx->sp_pidx.empty()) std::memcpy(pidx, ctx->sp_pidx.data(), ctx->sp_pidx.size() * sizeof(int32_t));
+    return WFSA_OK;
+}
+
+int wfsa_dev_sample_uniforms(int device, uint64_t seed, int64_t string, int32_t sample, int32_t n_draws, double* out) {
+    if (n_draws < 0 || sample < 0 || string < 0 || (!out && n_draws > 0)) return fail(WFSA_ERR_ARG, "sample_uniforms: bad arguments");
+    const hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail(WFSA_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (n_draws == 0) return WFSA_OK;
+    DevBuf<double> buf;
+    HIP_TRY(buf.alloc(size_t(n_draws)));
+    HIP_TRY(wfsa::launch_sample_uniforms(seed, uint64_t(string), uint32_t(sample), n_draws, buf.ptr, nullptr));
+    HIP_TRY(hipMemcpy(out, buf.ptr, size_t(n_draws) * sizeof(double), hipMemcpyDeviceToHost));
+    return WFSA_OK;
+}
 
 
 // Entry points that take part in rank collectives: a failure on this rank

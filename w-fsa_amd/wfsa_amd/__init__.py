@@ -24,7 +24,7 @@ def _ptr(a):
 
 
 __all__ = ["Fsa", "Corpus", "QuasiNewtonLearner", "Device", "Synthetic", "WfsaError", "load", "shard_range",
-           "sym_sparse_solve", "trellis_stats"]
+           "sym_sparse_solve", "trellis_stats", "sample_uniforms"]
 
 
 def shard_range(off, nranks, rank):
@@ -50,6 +50,15 @@ def sym_sparse_solve(i, j, v, n, b=None, order=0):
     return x, dict(positive=int(oi[0]), negative=int(oi[1]), nnz_l=int(oi[2]), ordered=bool(oi[3]),
                    supernodes=int(oi[4]), two_by_two=int(oi[5]), max_front=int(oi[6]), delayed=int(oi[7]),
                    log_abs_det=float(od[0]), det_sign=int(od[1]), min_pivot_ratio=float(od[2]))
+
+
+def sample_uniforms(seed, string, sample, n_draws, device=0):
+    """the uniforms the device's generator gives sample `sample` of string
+    `string` under `seed`, draws 0 .. n_draws - 1 (wfsa_dev_sample_uniforms:
+    Philox4x32-10, the contract in wfsa_dev.h) -- a test entry, no automaton"""
+    out = np.zeros(max(int(n_draws), 1), dtype=np.float64)
+    check_dev(load().wfsa_dev_sample_uniforms(int(device), int(seed), int(string), int(sample), int(n_draws), _ptr(out)))
+    return out[:int(n_draws)]
 
 
 def trellis_stats(fsa):
@@ -310,6 +319,22 @@ class QuasiNewtonLearner:
         check_host(load().wfsa_learner_kbest_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
         return srow, logw[:n_paths.value], prow, pidx[:n.value]
 
+    def SamplePaths(self, n, seed=0):
+        """n posterior samples per local recognized string at the current x:
+        (srow, logw, prow, pidx, logq) in KBestPaths' layout -- string s owns the
+        n paths srow[s]:srow[s + 1] in sample order (not sorted, duplicates
+        possible), logq[s] is its log q from the same pass; reproducible from
+        `seed`"""
+        n_paths, m = C.c_int64(), C.c_int64()
+        logq = np.zeros(self.info()["n_local_strings"], dtype=np.float64)
+        check_host(load().wfsa_learner_sample_paths(self._h, int(n), int(seed), _ptr(logq), C.byref(n_paths), C.byref(m)))
+        srow = np.zeros(len(logq) + 1, dtype=np.int64)
+        logw = np.zeros(max(n_paths.value, 1), dtype=np.float64)
+        prow = np.zeros(n_paths.value + 1, dtype=np.int64)
+        pidx = np.zeros(max(m.value, 1), dtype=np.int32)
+        check_host(load().wfsa_learner_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
+        return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
+
     def trimmed_index(self):
         a = np.zeros(self.info()["n_full"], dtype=np.int32)
         check_host(load().wfsa_learner_trimmed_index(self._h, _ptr(a)))
@@ -569,6 +594,29 @@ class Device:
         pidx = np.zeros(max(n.value, 1), dtype=np.int32)
         check_dev(load().wfsa_dev_kbest_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
         return srow, logw[:n_paths.value], prow, pidx[:n.value]
+
+    def sample_paths(self, w_full, n, seed=0):
+        """n independent draws per loaded string from the posterior over its
+        accepting paths at w_full, 1 <= n <= 64: (srow, logw, prow, pidx, logq)
+        -- string s owns the paths srow[s]:srow[s + 1], exactly n in sample
+        order when it has an accepting path of finite weight (none otherwise,
+        logq[s] = -inf), logw[t] is path t's log weight,
+        pidx[prow[t]:prow[t + 1]] its Fsa parameter ids in path order and
+        logq[s] the string's log q; exp(logw[t] - logq[s]) is path t's
+        posterior mass.  The same weights, n and seed give the same bytes, and
+        the first j samples of an n result are the j result"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        n_paths, m = C.c_int64(), C.c_int64()
+        logq = np.zeros(self.n_strings, dtype=np.float64)
+        check_dev(load().wfsa_dev_sample_paths(self._h, _ptr(w), int(n), int(seed), _ptr(logq), C.byref(n_paths), C.byref(m)))
+        srow = np.zeros(self.n_strings + 1, dtype=np.int64)
+        logw = np.zeros(max(n_paths.value, 1), dtype=np.float64)
+        prow = np.zeros(n_paths.value + 1, dtype=np.int64)
+        pidx = np.zeros(max(m.value, 1), dtype=np.int32)
+        check_dev(load().wfsa_dev_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
+        return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
 
     def comm_init(self, nranks, rank, unique_id):
         buf = (C.c_uint8 * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))
