@@ -129,6 +129,7 @@ typedef struct {
     double best_path_ms;       /* last wfsa_dev_best_paths call: device time of its kernels */
     double kbest_path_ms;      /* last wfsa_dev_kbest_paths call: device time of its kernels */
     double sample_path_ms;     /* last wfsa_dev_sample_paths call: device time of its kernels */
+    double posterior_count_ms; /* last wfsa_dev_posterior_counts call: device time of its kernels */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -307,6 +308,67 @@ int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow /* [n_strings + 1] */
  * of draw d = 0 .. n_draws - 1 of sample `sample` of string `string` under
  * `seed` (the counter and key above). */
 int wfsa_dev_sample_uniforms(int device, uint64_t seed, int64_t string, int32_t sample, int32_t n_draws, double* out);
+
+/* Posterior expected counts: the per-string E-step.  For every loaded string at
+ * w_full, under P(path | string) = exp(w(path)) / q_s:
+ *   logq[s]    = log q_s, -inf when the string has no accepting path of finite
+ *                weight (NULL allowed);
+ *   entropy[s] = -sum_path P log P >= 0 in nats, NaN where logq[s] = -inf (NULL
+ *                allowed);
+ *   *n_entries = entries of all rows (NULL allowed).
+ * posterior_counts_get copies the sparse rows out (any pointer may be NULL): a
+ * string of positive mass owns cidx[crow[s] .. crow[s + 1]), Fsa parameter ids
+ * in ascending order, each with cval > 0, the expected number of times a path
+ * of s uses that parameter (single-member groups carry no id, as everywhere);
+ * any other string owns nothing.  sum_s p_s * row_s is minus the gradient of
+ * the corpus log-likelihood before the constraints' projection, and
+ * entropy[s] = logq[s] - row_s . w.
+ *
+ * Arithmetic (posterior.hip).  The forward pass is sample_paths': log alpha per
+ * live node as the greatest term log alpha[src] + lw[edge] over its in-edges
+ * plus the log of the sum of exp(term - greatest) in the model's in-edge order,
+ * lw the decoders' edge log-weights; log q likewise over the end edges in (live
+ * slot, end edge) order: logq equals sample_paths' logq byte for byte.  The
+ * backward pass walks node posteriors from the last position down: in-edge e
+ * into node k at position i carries the mass
+ *   m_e = gamma_i[k] * exp(min(0, log alpha_{i-1}[src] + lw[e] - log alpha_i[k])),
+ * an end edge exp(min(0, log alpha_L[k] + lw[x] - log q)); a mass of 0 (an edge
+ * at -inf, a source of mass 0, an underflow) is skipped.  Every mass is rounded
+ * ONCE to fixed point and added with integer atomics, so the result does not
+ * depend on the order of arrival: node posteriors (<= 1) at 2^-62, counts at
+ * 2^-F with F = 62 - ceil(log2((max_len + 1) * longest edge parameter list)),
+ * the bound on any count (F = 62 when it is 1; 55 at 100).  A mass below half a
+ * unit rounds to 0 and is not added.  A parameter is listed when its
+ * accumulated fixed-point count is not 0; cval is that integer times 2^-F.
+ * Entropy is the chain-rule sum of -m * (the clamped exponent) over the same
+ * edges -- no cancellation -- per lane in a fixed order, then a butterfly sum.
+ * A string with exactly one accepting path of finite weight has every mass
+ * exp(0) = 1: its integer counts exactly and entropy exactly 0.
+ *
+ * Reproducibility: the same weights give the same bytes on every call,
+ * whatever the number of waves in flight and whichever wave took which string;
+ * the learning path's tiers play no part.
+ *
+ * Valid until the next load or posterior_counts call; best_paths, kbest_paths,
+ * sample_paths and posterior_counts results do not invalidate each other.
+ * Local to the rank (no collective), and leaves the learning path untouched,
+ * as the decoders do.  WFSA_ERR_ARG before a model and a corpus are loaded,
+ * while an evaluation is in flight, in matrix-file mode, and from _get without
+ * a result since the last load; WFSA_ERR_CAPACITY on the dense path (load with
+ * WFSA_DENSE=0), when one wave's scratch (the sampler's rows, two rows of
+ * n_nodes posteriors and n_params counts) exceeds the 1 GiB budget, and when
+ * the rows' entries exceed 4 GiB at 12 bytes an entry (a row is the union of
+ * the parameters over the string's paths, so its length is known only after
+ * the pass: the first call sizes the output for (total bytes + n_strings) * the
+ * longest edge parameter list entries, a pass whose rows do not fit still
+ * counts them, and one more pass at the exact size fills them in).
+ * (Environment, for measurements: WFSA_POSTERIOR_WAVES caps
+ * the waves in flight; WFSA_POSTERIOR_PHASES=1 runs the forward pass alone, =2
+ * leaves out the row scan -- timing only, such a call leaves no result.) */
+int wfsa_dev_posterior_counts(wfsa_dev* ctx, const double* w_full, double* logq /* [n_strings], NULL allowed */,
+                              double* entropy /* [n_strings], NULL allowed */, int64_t* n_entries /* NULL allowed */);
+int wfsa_dev_posterior_counts_get(wfsa_dev* ctx, int64_t* crow /* [n_strings + 1] */, int32_t* cidx /* [n_entries] */,
+                                  double* cval /* [n_entries] */);
 
 /* Where each loaded string runs (after compilation): tier[s] = -1 compiled
  * stream (trivial words + bubbles), 0 / 1 LDS-slab traversal, 2 wide

@@ -138,6 +138,17 @@ int wfsa_learner_sample_paths(wfsa_learner* l, int32_t n, uint64_t seed, double*
                               int64_t* n_paths, int64_t* n_entries);
 int wfsa_learner_sample_paths_get(wfsa_learner* l, int64_t* srow /* [n_local_strings + 1] */, double* logw /* [n_paths] */,
                                   int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
+/* Posterior expected counts at the current x (wfsa_dev_posterior_counts with
+ * w_full from GetWeight): per local recognized string, in get_p's order, its
+ * log q, the entropy of its path posterior (nats) and the sparse row of expected
+ * Fsa parameter counts; logq, entropy and n_entries may be NULL.
+ * posterior_counts_get copies the rows out: string s owns
+ * cidx[crow[s] .. crow[s + 1]), ascending ids, cval > 0.  Local to the rank: no
+ * collective. */
+int wfsa_learner_posterior_counts(wfsa_learner* l, double* logq /* [n_local_strings] */, double* entropy /* [n_local_strings] */,
+                                  int64_t* n_entries);
+int wfsa_learner_posterior_counts_get(wfsa_learner* l, int64_t* crow /* [n_local_strings + 1] */, int32_t* cidx /* [n_entries] */,
+                                      double* cval /* [n_entries] */);
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out);      /* [n_full]          */
 int wfsa_learner_path_counts(wfsa_learner* l, double* out, uint8_t* recognized); /* [shard size] */
 int wfsa_learner_renormalize(wfsa_learner* l);                      /* Learner::Renormalize */

@@ -623,4 +623,21 @@ void Learner::SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t
     ThrowOnDevError(rc, "wfsa_dev_sample_paths_get");
 }
 
+void Learner::PosteriorCounts(double* logq, double* entropy, int64_t* n_entries) {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
+    const double none = 0.0;
+    get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
+    const int rc = wfsa_dev_posterior_counts(dev, w_full.data(), logq, entropy, n_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_posterior_counts: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_posterior_counts");
+}
+
+void Learner::PosteriorCountsGet(int64_t* crow, int32_t* cidx, double* cval) const {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    const int rc = wfsa_dev_posterior_counts_get(dev, crow, cidx, cval);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_posterior_counts_get: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_posterior_counts_get");
+}
+
 }  // namespace wfsa

@@ -160,6 +160,13 @@ public:
     // string's n paths in sample order
     void SamplePaths(int32_t n, uint64_t seed, double* logq, int64_t* n_paths, int64_t* n_entries);
     void SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const;
+    // Posterior expected counts at the current x (wfsa_dev_posterior_counts
+    // with GetWeight's w_full): per local recognized string its log q, the
+    // entropy of its path posterior and the sparse row of expected parameter
+    // counts (logq, entropy, n_entries nullable).  PosteriorCountsGet copies
+    // the rows out: string s owns cidx[crow[s] .. crow[s + 1]), ascending ids
+    void PosteriorCounts(double* logq, double* entropy, int64_t* n_entries);
+    void PosteriorCountsGet(int64_t* crow, int32_t* cidx, double* cval) const;
     const std::vector<int32_t>& GetTrimmedIndex() const { return trimmed_weights; }
     const std::vector<double>& GetPathCounts() const { return path_count_local; }   // per local corpus string
     const std::vector<uint8_t>& GetRecognized() const { return recognized_local; }

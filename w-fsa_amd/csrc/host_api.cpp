@@ -444,6 +444,16 @@ int wfsa_learner_sample_paths_get(wfsa_learner* l, int64_t* srow, double* logw, 
     return guarded([&] { l->base->SamplePathsGet(srow, logw, prow, pidx); });
 }
 
+int wfsa_learner_posterior_counts(wfsa_learner* l, double* logq, double* entropy, int64_t* n_entries) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->host(false).PosteriorCounts(logq, entropy, n_entries); });   // (no collective: nothing to abort)
+}
+
+int wfsa_learner_posterior_counts_get(wfsa_learner* l, int64_t* crow, int32_t* cidx, double* cval) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->base->PosteriorCountsGet(crow, cidx, cval); });
+}
+
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out) {
     if (!l || !out) return null_arg("learner/out");
     const auto& v = l->base->GetTrimmedIndex();

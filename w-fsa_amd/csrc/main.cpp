@@ -4,7 +4,7 @@
 //
 //   wfsa -a A.wfsa -c C.corpus [-opt Hessian|QuasiNewton] [-e epochs] [-l eta]
 //        [-tol t] [-i flags] [-n] [-eval] [-s] [-o out.wfsa] [-x] [-p] [-bp best.tsv] [-kbp K kbest.tsv]
-//        [-sp N samples.tsv [--sample-seed S]] [-d device]
+//        [-sp N samples.tsv [--sample-seed S]] [-pc counts.tsv] [-d device]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -51,13 +51,16 @@ void usage() {
                  "  -sp, --sample-paths N FILE  likewise N (1 .. 64) paths drawn at random from its posterior, one line each:\n"
                  "                         string, sample index (0 first), log weight, weight / q, Fsa parameter indices in path order\n"
                  "  --sample-seed S        seed of -sp's random numbers (0); the same seed gives the same file\n"
+                 "  -pc, --posterior-counts FILE  likewise its posterior expected counts, one line per recognized string:\n"
+                 "                         string, log q, entropy of its path posterior (nats), then id:count per Fsa parameter\n"
+                 "                         used in expectation, ascending ids (tab separated)\n"
                  "  -d, --device N         GPU to use (0)\n";
 }
 
 }  // namespace
 
 int main(int argc, const char* argv[]) {
-    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths, sample_paths;
+    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths, sample_paths, posterior_counts;
     int epochs = 20, initflags = 0, device = 0, kbest = 0, n_samples = 0;
     unsigned long long sample_seed = 0;
     double eta = 1.0, tol = 1e-6;
@@ -93,6 +96,7 @@ int main(int argc, const char* argv[]) {
             n_samples = std::atoi(next());
             sample_paths = next();
         }
+        else if (a == "-pc" || a == "--posterior-counts") posterior_counts = next();
         else if (a == "--sample-seed") sample_seed = std::strtoull(next(), nullptr, 10);
         else if (a == "-n" || a == "--normalize") normalize = true;
         else if (a == "-eval" || a == "--eval" || a == "--evaluate") evaluate = true;
@@ -121,7 +125,7 @@ int main(int argc, const char* argv[]) {
         learner.SetDevice(device);
         Fsa fsa;
         bool have_fsa = false;
-        std::vector<std::string> recognized_strings;   // -bp / -kbp / -sp: the local recognized strings, in corpus order
+        std::vector<std::string> recognized_strings;   // -bp / -kbp / -sp / -pc: the local recognized strings, in corpus order
         if (!matrices.empty() && matrices.front() == '<') {   // src/main.cpp:123-137: skip Corpus and Fsa
             std::cerr << "Loading matrices \"" << matrices.substr(1) << "\" ... ";
             if (!learner.LoadMatrices(matrices.substr(1)))
@@ -176,7 +180,7 @@ int main(int argc, const char* argv[]) {
             for (const auto& word : corpus) rec.Recognize(word.first.c_str(), Path("", fsa.GetStartState()), recognize == 0);
         }
         learner.BuildFrom(fsa, corpus);
-        if (!best_paths.empty() || !kbest_paths.empty() || !sample_paths.empty()) {
+        if (!best_paths.empty() || !kbest_paths.empty() || !sample_paths.empty() || !posterior_counts.empty()) {
             const auto& rec = learner.GetRecognized();
             size_t s = 0;
             for (const auto& word : corpus) {
@@ -307,6 +311,25 @@ int main(int argc, const char* argv[]) {
                     std::fputc('\n', sf);
                 }
             std::fclose(sf);
+        }
+        if (!posterior_counts.empty()) {   // the per-string E-step at the final x
+            if (!have_fsa) throw MyError("-pc needs an automaton and a corpus (-a / -c): matrix-file mode has no trellis");
+            const size_t n = recognized_strings.size();
+            int64_t n_entries = 0;
+            std::vector<double> logq(n + 1), entropy(n + 1);
+            learner.PosteriorCounts(logq.data(), entropy.data(), &n_entries);
+            std::vector<int64_t> crow(n + 1);
+            std::vector<int32_t> cidx(size_t(n_entries) + 1);
+            std::vector<double> cval(size_t(n_entries) + 1);
+            learner.PosteriorCountsGet(crow.data(), cidx.data(), cval.data());
+            FILE* pf = std::fopen(posterior_counts.c_str(), "w");
+            if (!pf) throw MyError("Unable to open \"", posterior_counts, "\" for writing!");
+            for (size_t s = 0; s < n; ++s) {
+                std::fprintf(pf, "%s\t%.17g\t%.17g", recognized_strings[s].c_str(), logq[s], entropy[s]);
+                for (int64_t q = crow[s]; q < crow[s + 1]; ++q) std::fprintf(pf, "\t%d:%.17g", cidx[size_t(q)], cval[size_t(q)]);
+                std::fputc('\n', pf);
+            }
+            std::fclose(pf);
         }
         if (evaluate) {
             const auto results = learner.GetOptimizationResult(print);

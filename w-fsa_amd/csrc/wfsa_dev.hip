@@ -40,6 +40,7 @@
 #include "fb_kernels.hpp"
 #include "decode.hpp"
 #include "sample.hpp"
+#include "posterior.hpp"
 #include "trellis_model.hpp"
 
 namespace {
@@ -452,6 +453,18 @@ struct wfsa_dev {
     std::vector<int64_t> sp_srow, sp_prow;
     std::vector<double> sp_logw;
     std::vector<int32_t> sp_pidx;
+    // Posterior expected counts (wfsa_dev_posterior_counts; posterior.hpp): a
+    // fourth buffer set, plus the stored rows, the fixed-point gamma and count
+    // rows, log q, entropy, the cursor and the rows as the waves left them --
+    // and its last result for _get, rows in string order
+    DecodeBufs pc;
+    DevBuf<double> pc_hist, pc_logq, pc_ent, pc_val;
+    DevBuf<unsigned long long> pc_gamma, pc_count, pc_cursor;
+    DevBuf<int64_t> pc_start;
+    DevBuf<int32_t> pc_len, pc_idx;
+    std::vector<int64_t> pc_crow;
+    std::vector<int32_t> pc_cidx;
+    std::vector<double> pc_cval;
     std::vector<int64_t> bp_prow;
     std::vector<int32_t> bp_pidx;
     std::vector<int64_t> kb_srow, kb_prow;
@@ -2995,7 +3008,7 @@ void drop_graph(wfsa_dev* ctx) {
 }
 
 // a load ends the decode results held for _get
-void invalidate_decodes(wfsa_dev* ctx) { ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = false; }
+void invalidate_decodes(wfsa_dev* ctx) { ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = ctx->pc.valid = false; }
 
 // weights in / results out, sized by n_params
 int alloc_param_buffers(wfsa_dev* ctx) {
@@ -3143,7 +3156,7 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     if (ctx->flag) (void)hipHostFree(ctx->flag);
     for (hipEvent_t ev : {ctx->ev0, ctx->ev1})
         if (ev) (void)hipEventDestroy(ev);
-    for (DecodeBufs* d : {&ctx->bp, &ctx->kb, &ctx->sp})
+    for (DecodeBufs* d : {&ctx->bp, &ctx->kb, &ctx->sp, &ctx->pc})
         for (hipEvent_t ev : {d->ev0, d->ev1})
             if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
@@ -4782,6 +4795,182 @@ int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_
     if (logw && !ctx->sp_logw.empty()) std::memcpy(logw, ctx->sp_logw.data(), ctx->sp_logw.size() * sizeof(double));
     if (prow) std::memcpy(prow, ctx->sp_prow.data(), ctx->sp_prow.size() * sizeof(int64_t));
     if (pidx && !ctx->sp_pidx.empty()) std::memcpy(pidx, ctx->sp_pidx.data(), ctx->sp_pidx.size() * sizeof(int32_t));
+    return WFSA_OK;
+}
+
+// Posterior expected counts (posterior.hpp): per string log q, the entropy of
+// its path posterior and the sparse row of expected parameter counts, with the
+// sampler's checks and waves in flight and buffers of its own (the context's
+// `pc`).  The waves leave the rows in the order they finished; the host puts
+// them into string order.
+int wfsa_dev_posterior_counts(wfsa_dev* ctx, const double* w_full, double* logq, double* entropy, int64_t* n_entries) {
+    const char* name = "posterior_counts";
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to walk", name);
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (ctx->dense)
+        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to take its posterior", name);
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    DecodeBufs& d = ctx->pc;
+    d.valid = false;
+    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
+    // the longest edge parameter list bounds a count ((max_len + 1) edges a path) and a row; every id indexes the count row
+    int64_t max_list = 1;
+    for (size_t g = 0; g + 1 < ctx->h_pptr.size(); ++g) max_list = std::max<int64_t>(max_list, ctx->h_pptr[g + 1] - ctx->h_pptr[g]);
+    for (int32_t j : ctx->h_pidx)
+        if (j < 0 || j >= np) return fail(WFSA_ERR_MODEL, "%s: parameter id %d on an edge list is outside 0 .. %d", name, int(j), int(np) - 1);
+    const int frac = wfsa::posterior_count_frac((int64_t(ctx->max_len) + 1) * max_list);
+    const int64_t wave_bytes = wfsa::posterior_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst, np);
+    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
+    if (fit < 1)
+        return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations, %d parameters) exceeds the budget",
+                    name, (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst, int(np));
+    // Room for the rows.  One path uses at most (L + 1) x max_list parameters, but a row is the union over
+    // the string's paths: that figure only sizes the first attempt.  A launch whose rows do not fit still
+    // counts them (the cursor ends at the exact total), and one more launch at that size fills them in.
+    constexpr int64_t kOutBudget = int64_t(4) << 30;   // bytes of ids and values
+    const int64_t cap_max = std::max<int64_t>(1, S * int64_t(std::max(np, 1)));
+    int64_t cap = std::min<int64_t>(cap_max, std::max<int64_t>({1, (ctx->total_sym + S) * max_list, int64_t(ctx->pc_idx.n)}));
+    cap = std::min<int64_t>(cap, kOutBudget / 12);
+    int phases = 3;   // WFSA_POSTERIOR_PHASES=1 / 2: timing only (forward pass alone / no row scan), no result
+    if (const char* e = std::getenv("WFSA_POSTERIOR_PHASES")) phases = std::max(1, std::min(3, std::atoi(e)));
+    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
+    int64_t max_waves = 16 * int64_t(ctx->n_cu);
+    if (const char* e = std::getenv("WFSA_POSTERIOR_WAVES")) max_waves = std::max<int64_t>(1, std::min<int64_t>(max_waves, std::atoll(e)));
+    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({max_waves, fit, S}));
+    const int grid = int(std::max<int64_t>(1, waves / wpb));
+    const int64_t n_waves = int64_t(grid) * wpb;
+    hipStream_t s = ctx->stream;
+    if (!d.ev0) {
+        HIP_TRY(hipEventCreate(&d.ev0));
+        HIP_TRY(hipEventCreate(&d.ev1));
+    }
+    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
+    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    const int64_t hist = int64_t(std::max(ctx->max_len, 1)) * int64_t(std::max(ctx->max_dst, 1));
+    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
+    HIP_TRY(d.lw.alloc(size_t(E + X)));
+    HIP_TRY(d.score.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(ctx->pc_hist.alloc(size_t(n_waves * hist)));
+    HIP_TRY(ctx->pc_gamma.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(ctx->pc_count.alloc(size_t(n_waves * int64_t(std::max(np, 1)))));
+    HIP_TRY(d.ctr.alloc(1));
+    HIP_TRY(ctx->pc_cursor.alloc(2));
+    HIP_TRY(ctx->pc_logq.alloc(size_t(S)));
+    HIP_TRY(ctx->pc_ent.alloc(size_t(S)));
+    HIP_TRY(ctx->pc_start.alloc(size_t(S)));
+    HIP_TRY(ctx->pc_len.alloc(size_t(S)));
+    wfsa::PosteriorArgs a{};
+    a.d.w.c_ptr = ctx->w_cptr.ptr;
+    a.d.w.dst = ctx->w_dst.ptr;
+    a.d.w.e_ptr = ctx->w_eptr.ptr;
+    a.d.w.e_src = ctx->w_esrc.ptr;
+    a.d.w.e_g = ctx->w_eg.ptr;
+    a.d.x_ptr = ctx->x_ptr.ptr;
+    a.d.pptr = ctx->pptr.ptr;
+    a.d.pidx = ctx->pidx.ptr;
+    a.d.n_nodes = ctx->n_nodes;
+    a.d.start = ctx->start;
+    a.d.n_edges = int32_t(E);
+    a.d.n_end = int32_t(X);
+    a.d.sym = ctx->sym.ptr;
+    a.d.off = ctx->off.ptr;
+    a.d.n_strings = int32_t(S);
+    a.d.max_len = ctx->max_len;
+    a.d.max_dst = ctx->max_dst;
+    a.d.k = 1;
+    a.d.wt = d.w.ptr;
+    a.d.lw = d.lw.ptr;
+    a.d.score = d.score.ptr;
+    a.d.back = nullptr;   // (no back-pointers, weights or paths: the rows below instead)
+    a.d.ctr = d.ctr.ptr;
+    a.d.best = nullptr;
+    a.d.path = nullptr;
+    a.hist = ctx->pc_hist.ptr;
+    a.gamma = ctx->pc_gamma.ptr;
+    a.count = ctx->pc_count.ptr;
+    a.n_params = np;
+    a.count_frac = frac;
+    a.phases = phases;
+    a.logq = ctx->pc_logq.ptr;
+    a.entropy = ctx->pc_ent.ptr;
+    a.cursor = ctx->pc_cursor.ptr;
+    a.row_start = ctx->pc_start.ptr;
+    a.row_len = ctx->pc_len.ptr;
+    std::vector<double> lq(size_t(S), 0.0), ent(size_t(S), 0.0);
+    std::vector<int64_t> start(size_t(S), 0);
+    std::vector<int32_t> len(size_t(S), 0);
+    unsigned long long cur[2] = {0, 0};
+    for (int attempt = 0;; ++attempt) {
+        HIP_TRY(ctx->pc_idx.alloc(size_t(cap)));
+        HIP_TRY(ctx->pc_val.alloc(size_t(cap)));
+        a.capacity = cap;
+        a.out_idx = ctx->pc_idx.ptr;
+        a.out_val = ctx->pc_val.ptr;
+        HIP_TRY(hipEventRecord(d.ev0, s));
+        HIP_TRY(wfsa::launch_posterior_counts(a, grid, wpb, s));
+        HIP_TRY(hipEventRecord(d.ev1, s));
+        HIP_TRY(ctx->pc_cursor.download(cur, 2, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (phases < 3 || cur[1] == 0) break;
+        // some row did not fit: the cursor holds the entries all rows need
+        const int64_t need = int64_t(cur[0]);
+        if (attempt > 0 || need <= cap || need > cap_max)
+            return fail(WFSA_ERR_HIP, "%s: the rows took %lld entries at a capacity of %lld (at most %lld possible)", name, (long long)need,
+                        (long long)cap, (long long)cap_max);
+        if (need > kOutBudget / 12)
+            return fail(WFSA_ERR_CAPACITY, "%s: the rows take %lld entries (%lld strings, %d parameters), over the %lld-byte budget", name,
+                        (long long)need, (long long)S, int(np), (long long)kOutBudget);
+        cap = need;
+    }
+    HIP_TRY(ctx->pc_logq.download(lq.data(), size_t(S), s));
+    HIP_TRY(ctx->pc_ent.download(ent.data(), size_t(S), s));
+    HIP_TRY(ctx->pc_start.download(start.data(), size_t(S), s));
+    HIP_TRY(ctx->pc_len.download(len.data(), size_t(S), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    ctx->stats.posterior_count_ms = double(ms);
+    ctx->pc_crow.assign(size_t(S) + 1, 0);
+    ctx->pc_cidx.clear();
+    ctx->pc_cval.clear();
+    if (phases == 3) {
+        const size_t total = size_t(cur[0]);
+        std::vector<int32_t> idx(total);
+        std::vector<double> val(total);
+        HIP_TRY(ctx->pc_idx.download(idx.data(), total, s));
+        HIP_TRY(ctx->pc_val.download(val.data(), total, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ctx->pc_cidx.resize(total);
+        ctx->pc_cval.resize(total);
+        size_t at = 0;
+        for (int64_t i = 0; i < S; ++i) {
+            const int64_t b = start[size_t(i)], n = len[size_t(i)];
+            if (n < 0 || b < 0 || b + n > int64_t(total) || at + size_t(n) > total)
+                return fail(WFSA_ERR_HIP, "%s: string %lld: row [%lld, +%lld) lies outside the %zu entries handed out", name, (long long)i,
+                            (long long)b, (long long)n, total);
+            std::copy(idx.begin() + b, idx.begin() + b + n, ctx->pc_cidx.begin() + at);
+            std::copy(val.begin() + b, val.begin() + b + n, ctx->pc_cval.begin() + at);
+            at += size_t(n);
+            ctx->pc_crow[size_t(i) + 1] = int64_t(at);
+        }
+        if (at != total) return fail(WFSA_ERR_HIP, "%s: the rows hold %zu entries, the cursor handed out %zu", name, at, total);
+        d.valid = true;
+    }
+    if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
+    if (entropy && S > 0) std::memcpy(entropy, ent.data(), size_t(S) * sizeof(double));
+    if (n_entries) *n_entries = int64_t(ctx->pc_cidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_posterior_counts_get(wfsa_dev* ctx, int64_t* crow, int32_t* cidx, double* cval) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->pc.valid) return fail(WFSA_ERR_ARG, "posterior_counts_get: no wfsa_dev_posterior_counts result since the last load");
+    if (crow) std::memcpy(crow, ctx->pc_crow.data(), ctx->pc_crow.size() * sizeof(int64_t));
+    if (cidx && !ctx->pc_cidx.empty()) std::memcpy(cidx, ctx->pc_cidx.data(), ctx->pc_cidx.size() * sizeof(int32_t));
+    if (cval && !ctx->pc_cval.empty()) std::memcpy(cval, ctx->pc_cval.data(), ctx->pc_cval.size() * sizeof(double));
     return WFSA_OK;
 }
 

@@ -335,6 +335,23 @@ class QuasiNewtonLearner:
         check_host(load().wfsa_learner_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
         return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
 
+    def PosteriorCounts(self):
+        """the per-string E-step at the current x, per local recognized string:
+        (crow, cidx, cval, logq, entropy) -- string s owns the ascending Fsa
+        parameter ids cidx[crow[s]:crow[s + 1]] with their expected counts cval
+        under its path posterior, logq[s] is its log q and entropy[s] the
+        posterior's entropy in nats"""
+        m = C.c_int64()
+        n = self.info()["n_local_strings"]
+        logq = np.zeros(n, dtype=np.float64)
+        ent = np.zeros(n, dtype=np.float64)
+        check_host(load().wfsa_learner_posterior_counts(self._h, _ptr(logq), _ptr(ent), C.byref(m)))
+        crow = np.zeros(n + 1, dtype=np.int64)
+        cidx = np.zeros(max(m.value, 1), dtype=np.int32)
+        cval = np.zeros(max(m.value, 1), dtype=np.float64)
+        check_host(load().wfsa_learner_posterior_counts_get(self._h, _ptr(crow), _ptr(cidx), _ptr(cval)))
+        return crow, cidx[:m.value], cval[:m.value], logq, ent
+
     def trimmed_index(self):
         a = np.zeros(self.info()["n_full"], dtype=np.int32)
         check_host(load().wfsa_learner_trimmed_index(self._h, _ptr(a)))
@@ -617,6 +634,28 @@ class Device:
         pidx = np.zeros(max(m.value, 1), dtype=np.int32)
         check_dev(load().wfsa_dev_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
         return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
+
+    def posterior_counts(self, w_full):
+        """the per-string E-step at w_full: (crow, cidx, cval, logq, entropy) --
+        a string with an accepting path of finite weight owns the ascending Fsa
+        parameter ids cidx[crow[s]:crow[s + 1]], each with cval > 0, the
+        expected number of times a path of s uses it under
+        exp(w(path)) / q_s; logq[s] is its log q (sample_paths' bytes) and
+        entropy[s] >= 0 the posterior's entropy in nats.  Any other string owns
+        nothing, with logq = -inf and entropy NaN.  The same weights give the
+        same bytes on every call (fixed-point sums: the contract in wfsa_dev.h)"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        m = C.c_int64()
+        logq = np.zeros(self.n_strings, dtype=np.float64)
+        ent = np.zeros(self.n_strings, dtype=np.float64)
+        check_dev(load().wfsa_dev_posterior_counts(self._h, _ptr(w), _ptr(logq), _ptr(ent), C.byref(m)))
+        crow = np.zeros(self.n_strings + 1, dtype=np.int64)
+        cidx = np.zeros(max(m.value, 1), dtype=np.int32)
+        cval = np.zeros(max(m.value, 1), dtype=np.float64)
+        check_dev(load().wfsa_dev_posterior_counts_get(self._h, _ptr(crow), _ptr(cidx), _ptr(cval)))
+        return crow, cidx[:m.value], cval[:m.value], logq, ent
 
     def comm_init(self, nranks, rank, unique_id):
         buf = (C.c_uint8 * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))

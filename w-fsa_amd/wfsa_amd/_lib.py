@@ -52,7 +52,7 @@ class DevStats(C.Structure):
         ("stream_block", i32), ("stream_w_lds", i32), ("stream_wide", i32), ("stream_multi", i32),
         ("stream_delta", i32), ("bubbles_fused", i32), ("grad_tables", i32), ("wave_lgrad", i32),
         ("ll_dot_launches", i64), ("best_path_ms", dbl), ("kbest_path_ms", dbl),
-        ("sample_path_ms", dbl),
+        ("sample_path_ms", dbl), ("posterior_count_ms", dbl),
     ]
 
 
@@ -87,6 +87,8 @@ _SIGS = {
     "wfsa_dev_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_sample_paths": (C.c_int, [vp, vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
     "wfsa_dev_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
+    "wfsa_dev_posterior_counts": (C.c_int, [vp, vp, vp, vp, P(i64)]),
+    "wfsa_dev_posterior_counts_get": (C.c_int, [vp, vp, vp, vp]),
     "wfsa_dev_sample_uniforms": (C.c_int, [C.c_int, C.c_uint64, i64, C.c_int32, C.c_int32, vp]),
     "wfsa_dev_sym_factor": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp]),
     "wfsa_dev_sym_solve": (C.c_int, [vp, vp]),
@@ -151,6 +153,8 @@ _SIGS = {
     "wfsa_learner_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_learner_sample_paths": (C.c_int, [vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
     "wfsa_learner_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
+    "wfsa_learner_posterior_counts": (C.c_int, [vp, vp, vp, P(i64)]),
+    "wfsa_learner_posterior_counts_get": (C.c_int, [vp, vp, vp, vp]),
     "wfsa_learner_trimmed_index": (C.c_int, [vp, vp]),
     "wfsa_learner_path_counts": (C.c_int, [vp, vp, vp]),
     "wfsa_learner_renormalize": (C.c_int, [vp]),
