@@ -130,6 +130,7 @@ typedef struct {
     double kbest_path_ms;      /* last wfsa_dev_kbest_paths call: device time of its kernels */
     double sample_path_ms;     /* last wfsa_dev_sample_paths call: device time of its kernels */
     double posterior_count_ms; /* last wfsa_dev_posterior_counts call: device time of its kernels */
+    double byte_marginal_ms;   /* last wfsa_dev_byte_marginals call: device time of its kernels */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -369,6 +370,83 @@ int wfsa_dev_posterior_counts(wfsa_dev* ctx, const double* w_full, double* logq 
                               double* entropy /* [n_strings], NULL allowed */, int64_t* n_entries /* NULL allowed */);
 int wfsa_dev_posterior_counts_get(wfsa_dev* ctx, int64_t* crow /* [n_strings + 1] */, int32_t* cidx /* [n_entries] */,
                                   double* cval /* [n_entries] */);
+
+/* Per-byte state posteriors and the max-expected-accuracy (MEA) decode.  For a
+ * loaded string s of L bytes at w_full, under P(path | s) = exp(w(path)) / q_s:
+ *   mass[s, i, U], i = 1 .. L: the posterior probability that byte i of s lies
+ *     inside an emission of Fsa state U (a state id in wfsa_model_desc
+ *     numbering).  States with the empty emission emit no byte and never appear;
+ *     for every byte the sum over U is 1.
+ *   boundary[s, i]: the posterior probability that an emission ends with byte i;
+ *     boundary[s, L] is 1, and a byte strictly inside a multi-byte emission on
+ *     every path has boundary 0.
+ *   MEA decode (decode != 0): the accepting path of finite weight that maximises
+ *     score = sum_i mass[s, i, state of the path at byte i], the expected number
+ *     of bytes the returned analysis attributes to the same state as a path drawn
+ *     from the posterior; 0 < score <= L.
+ * Outputs (every pointer may be NULL):
+ *   logq[s]       log q_s, posterior_counts' logq byte for byte;
+ *   boundary[b]   for corpus byte b = off[s] + i - 1;
+ *   score[s], path_logw[s]  the MEA path's score and log weight (decode != 0
+ *                 only; untouched otherwise);
+ *   *n_entries    entries of all mass rows; *n_path_entries: total length of
+ *                 the paths' parameter lists (0 without decode).
+ * byte_marginals_get copies the sparse mass rows out: corpus byte b owns
+ * midx[mrow[b] .. mrow[b + 1]), state ids ascending, each with mval > 0.
+ * byte_marginals_path_get copies the MEA paths out in best_paths_get's layout
+ * (pidx[prow[s] .. prow[s + 1]) the Fsa parameter ids of string s's path in path
+ * order); WFSA_ERR_ARG when the last call had decode = 0.
+ * A string without an accepting path of finite weight owns nothing: logq = -inf,
+ * boundary NaN on its bytes, score NaN, path_logw -inf, empty rows, empty path.
+ *
+ * Arithmetic (marginals.hip).  posterior_counts' forward pass and backward gamma
+ * recursion, restated: log alpha is the greatest term plus the log of the sum of
+ * exp(term - greatest) in the model's in-edge order, log q likewise over the end
+ * edges in (live slot, end edge) order; in-edge e into node k at position i
+ * carries m_e = gamma_i[k] * exp(min(0, log alpha_{i-1}[src] + lw[e] - log
+ * alpha_i[k])); every mass is rounded ONCE to a multiple of 2^-62 and added with
+ * 64-bit integer atomics; a mass of 0 is skipped.  Being at node k at position i
+ * means, for a state, that an emission of it ended with byte i, and for a chain
+ * node that byte i lies inside the emission it spells: mass[s, i, U] is the
+ * integer sum of the fixed-point gamma_i over the nodes U owns, clamped to 2^62,
+ * and boundary[s, i] the integer sum over the state nodes, clamped likewise and
+ * converted once.  A state is listed when its fixed-point sum is not 0; mval is
+ * that integer times 2^-62.  Each sum is stored at a fixed address, a function
+ * of the corpus alone (the prefix sum over the corpus bytes of the number of
+ * distinct owner states among the byte's destinations, plus the state's rank
+ * among them), so the same weights give the same bytes on every call, whatever
+ * the number of waves in flight and whichever wave took which string.
+ * The decode is best_paths' (max, +) pass with a node reward in place of the
+ * edge weight: the reward of a destination at byte i is mass[s, i, its owner],
+ * an in-edge is eligible when its log weight is finite and its source's score is
+ * above -inf, and a destination's score is the best eligible source score plus
+ * its reward (one add per position, left to right).  Ties: in-edges by (source
+ * score descending, log weight descending, in-edge ascending); at the end by
+ * (score descending, node ascending) over the nodes with a finite end edge, then
+ * that node's end edges by (log weight descending, end edge ascending).
+ * path_logw is the decoders' left-to-right sum of the edge log-weights: the path
+ * carries bit for bit the weight kbest_paths reports for it.
+ * A string with exactly one accepting path of finite weight has every mass
+ * exactly 1.0, one entry per byte, boundaries exactly 0.0 or 1.0, score exactly
+ * L, and best_paths' path.
+ *
+ * Valid until the next load or byte_marginals call; best_paths, kbest_paths,
+ * sample_paths, posterior_counts and byte_marginals results do not invalidate
+ * each other.  Local to the rank (no collective), and leaves the learning path
+ * untouched, as the decoders do.  WFSA_ERR_ARG before a model and a corpus are
+ * loaded, while an evaluation is in flight, in matrix-file mode, and from _get
+ * without a result since the last load; WFSA_ERR_CAPACITY on the dense path
+ * (load with WFSA_DENSE=0), when one wave's scratch (the sampler's rows, two
+ * rows of n_nodes posteriors and, with decode, max_len x max_dst back-pointers)
+ * exceeds the 1 GiB budget, and when the state sums (8 bytes each) exceed 4 GiB.
+ * (Environment, for measurements: WFSA_MARGINAL_WAVES caps the waves in
+ * flight.) */
+int wfsa_dev_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t decode, double* logq /* [n_strings] */,
+                            double* boundary /* [total_symbols] */, double* score /* [n_strings] */,
+                            double* path_logw /* [n_strings] */, int64_t* n_entries, int64_t* n_path_entries);
+int wfsa_dev_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow /* [total_symbols + 1] */, int32_t* midx /* [n_entries] */,
+                                double* mval /* [n_entries] */);
+int wfsa_dev_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow /* [n_strings + 1] */, int32_t* pidx /* [n_path_entries] */);
 
 /* Where each loaded string runs (after compilation): tier[s] = -1 compiled
  * stream (trivial words + bubbles), 0 / 1 LDS-slab traversal, 2 wide

@@ -27,6 +27,8 @@ void wfsa_fsa_free(wfsa_fsa* fsa);
 int wfsa_fsa_desc(wfsa_fsa* fsa, wfsa_model_desc* out);
 /* counts: states, transitions, emissions, parameters, constraints, free params */
 int wfsa_fsa_counts(wfsa_fsa* fsa, int64_t out[6]);
+/* state id (wfsa_model_desc numbering, 0 .. states - 1) -> its name (valid while fsa lives) */
+int wfsa_fsa_state_name(wfsa_fsa* fsa, int32_t state, const char** name);
 /* Fsa parameter j -> owning state name, kind (0 emission / 1 transition), label */
 int wfsa_fsa_param_name(wfsa_fsa* fsa, int32_t j, const char** state, int32_t* kind, const char** label);
 
@@ -149,6 +151,22 @@ int wfsa_learner_posterior_counts(wfsa_learner* l, double* logq /* [n_local_stri
                                   int64_t* n_entries);
 int wfsa_learner_posterior_counts_get(wfsa_learner* l, int64_t* crow /* [n_local_strings + 1] */, int32_t* cidx /* [n_entries] */,
                                       double* cval /* [n_entries] */);
+/* Per-byte state posteriors and the MEA decode at the current x
+ * (wfsa_dev_byte_marginals with w_full from GetWeight) over the local
+ * recognized strings, in get_p's order, their bytes back to back (n_local_bytes
+ * in all): logq per string, boundary per byte and, with decode != 0, the MEA
+ * path's score and log weight per string; every pointer may be NULL.
+ * byte_marginals_get copies the mass rows out: byte b owns the state ids
+ * midx[mrow[b] .. mrow[b + 1]) (wfsa_fsa_state_name gives their names),
+ * ascending, mval > 0.  byte_marginals_path_get copies the MEA paths out in
+ * best_paths_get's layout; it fails after a call with decode = 0.  Local to the
+ * rank: no collective. */
+int wfsa_learner_byte_marginals(wfsa_learner* l, int32_t decode, double* logq /* [n_local_strings] */,
+                                double* boundary /* [n_local_bytes] */, double* score /* [n_local_strings] */,
+                                double* path_logw /* [n_local_strings] */, int64_t* n_entries, int64_t* n_path_entries);
+int wfsa_learner_byte_marginals_get(wfsa_learner* l, int64_t* mrow /* [n_local_bytes + 1] */, int32_t* midx /* [n_entries] */,
+                                    double* mval /* [n_entries] */);
+int wfsa_learner_byte_marginals_path_get(wfsa_learner* l, int64_t* prow /* [n_local_strings + 1] */, int32_t* pidx /* [n_path_entries] */);
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out);      /* [n_full]          */
 int wfsa_learner_path_counts(wfsa_learner* l, double* out, uint8_t* recognized); /* [shard size] */
 int wfsa_learner_renormalize(wfsa_learner* l);                      /* Learner::Renormalize */

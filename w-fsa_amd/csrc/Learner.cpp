@@ -640,4 +640,29 @@ void Learner::PosteriorCountsGet(int64_t* crow, int32_t* cidx, double* cval) con
     ThrowOnDevError(rc, "wfsa_dev_posterior_counts_get");
 }
 
+void Learner::ByteMarginals(bool decode, double* logq, double* boundary, double* score, double* path_logw, int64_t* n_entries,
+                            int64_t* n_path_entries) {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
+    const double none = 0.0;
+    get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
+    const int rc = wfsa_dev_byte_marginals(dev, w_full.data(), decode ? 1 : 0, logq, boundary, score, path_logw, n_entries, n_path_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_byte_marginals: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_byte_marginals");
+}
+
+void Learner::ByteMarginalsGet(int64_t* mrow, int32_t* midx, double* mval) const {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    const int rc = wfsa_dev_byte_marginals_get(dev, mrow, midx, mval);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_byte_marginals_get: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_byte_marginals_get");
+}
+
+void Learner::ByteMarginalsPathGet(int64_t* prow, int32_t* pidx) const {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    const int rc = wfsa_dev_byte_marginals_path_get(dev, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_byte_marginals_path_get: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_byte_marginals_path_get");
+}
+
 }  // namespace wfsa

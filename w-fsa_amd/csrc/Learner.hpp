@@ -167,6 +167,17 @@ public:
     // the rows out: string s owns cidx[crow[s] .. crow[s + 1]), ascending ids
     void PosteriorCounts(double* logq, double* entropy, int64_t* n_entries);
     void PosteriorCountsGet(int64_t* crow, int32_t* cidx, double* cval) const;
+    // Per-byte state posteriors at the current x (wfsa_dev_byte_marginals with
+    // GetWeight's w_full) over the local recognized strings, bytes back to
+    // back in string order: logq per string, boundary per byte and, with
+    // decode, the MEA path's score and log weight per string (every pointer
+    // nullable).  ByteMarginalsGet copies the mass rows out: byte b owns the
+    // state ids midx[mrow[b] .. mrow[b + 1]), ascending, mval > 0;
+    // ByteMarginalsPathGet the MEA paths in BestPathsGet's layout
+    void ByteMarginals(bool decode, double* logq, double* boundary, double* score, double* path_logw, int64_t* n_entries,
+                       int64_t* n_path_entries);
+    void ByteMarginalsGet(int64_t* mrow, int32_t* midx, double* mval) const;
+    void ByteMarginalsPathGet(int64_t* prow, int32_t* pidx) const;
     const std::vector<int32_t>& GetTrimmedIndex() const { return trimmed_weights; }
     const std::vector<double>& GetPathCounts() const { return path_count_local; }   // per local corpus string
     const std::vector<uint8_t>& GetRecognized() const { return recognized_local; }

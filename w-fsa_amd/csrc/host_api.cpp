@@ -154,6 +154,15 @@ int wfsa_fsa_counts(wfsa_fsa* f, int64_t out[6]) {
     return WFSA_OK;
 }
 
+int wfsa_fsa_state_name(wfsa_fsa* f, int32_t state, const char** name) {
+    if (!f || !name) return null_arg("fsa/name");
+    return guarded([&] {
+        if (!f->flat) f->flat.reset(new FlatModel(f->fsa));
+        if (state < 0 || size_t(state) >= f->flat->state_names.size()) throw FsaError("state index ", state, " out of range");
+        *name = f->flat->state_names[size_t(state)];
+    });
+}
+
 int wfsa_fsa_param_name(wfsa_fsa* f, int32_t j, const char** state, int32_t* kind, const char** label) {
     if (!f || !state || !kind || !label) return null_arg("fsa/outputs");
     return guarded([&] {
@@ -452,6 +461,24 @@ int wfsa_learner_posterior_counts(wfsa_learner* l, double* logq, double* entropy
 int wfsa_learner_posterior_counts_get(wfsa_learner* l, int64_t* crow, int32_t* cidx, double* cval) {
     if (!l) return null_arg("learner");
     return guarded([&] { l->base->PosteriorCountsGet(crow, cidx, cval); });
+}
+
+int wfsa_learner_byte_marginals(wfsa_learner* l, int32_t decode, double* logq, double* boundary, double* score, double* path_logw,
+                                int64_t* n_entries, int64_t* n_path_entries) {
+    if (!l) return null_arg("learner");
+    return guarded([&] {   // (no collective: nothing to abort)
+        l->host(false).ByteMarginals(decode != 0, logq, boundary, score, path_logw, n_entries, n_path_entries);
+    });
+}
+
+int wfsa_learner_byte_marginals_get(wfsa_learner* l, int64_t* mrow, int32_t* midx, double* mval) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->base->ByteMarginalsGet(mrow, midx, mval); });
+}
+
+int wfsa_learner_byte_marginals_path_get(wfsa_learner* l, int64_t* prow, int32_t* pidx) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->base->ByteMarginalsPathGet(prow, pidx); });
 }
 
 int wfsa_learner_trimmed_index(wfsa_learner* l, int32_t* out) {

@@ -54,13 +54,20 @@ void usage() {
                  "  -pc, --posterior-counts FILE  likewise its posterior expected counts, one line per recognized string:\n"
                  "                         string, log q, entropy of its path posterior (nats), then id:count per Fsa parameter\n"
                  "                         used in expectation, ascending ids (tab separated)\n"
+                 "  -bm, --byte-marginals FILE  likewise its per-byte state posteriors, one line per recognized string:\n"
+                 "                         string, log q, then per byte its boundary probability and the state-name:mass list\n"
+                 "                         (comma separated, ascending state ids), the fields tab separated\n"
+                 "  -md, --mea-decode FILE  likewise its max-expected-accuracy path (the analysis with the most bytes attributed\n"
+                 "                         to the right state in expectation), one line per recognized string:\n"
+                 "                         string, score, log weight, Fsa parameter indices in path order (tab separated)\n"
                  "  -d, --device N         GPU to use (0)\n";
 }
 
 }  // namespace
 
 int main(int argc, const char* argv[]) {
-    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths, sample_paths, posterior_counts;
+    std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths, sample_paths, posterior_counts, byte_marginals,
+        mea_decode;
     int epochs = 20, initflags = 0, device = 0, kbest = 0, n_samples = 0;
     unsigned long long sample_seed = 0;
     double eta = 1.0, tol = 1e-6;
@@ -97,6 +104,8 @@ int main(int argc, const char* argv[]) {
             sample_paths = next();
         }
         else if (a == "-pc" || a == "--posterior-counts") posterior_counts = next();
+        else if (a == "-bm" || a == "--byte-marginals") byte_marginals = next();
+        else if (a == "-md" || a == "--mea-decode") mea_decode = next();
         else if (a == "--sample-seed") sample_seed = std::strtoull(next(), nullptr, 10);
         else if (a == "-n" || a == "--normalize") normalize = true;
         else if (a == "-eval" || a == "--eval" || a == "--evaluate") evaluate = true;
@@ -180,7 +189,8 @@ int main(int argc, const char* argv[]) {
             for (const auto& word : corpus) rec.Recognize(word.first.c_str(), Path("", fsa.GetStartState()), recognize == 0);
         }
         learner.BuildFrom(fsa, corpus);
-        if (!best_paths.empty() || !kbest_paths.empty() || !sample_paths.empty() || !posterior_counts.empty()) {
+        if (!best_paths.empty() || !kbest_paths.empty() || !sample_paths.empty() || !posterior_counts.empty() || !byte_marginals.empty() ||
+            !mea_decode.empty()) {
             const auto& rec = learner.GetRecognized();
             size_t s = 0;
             for (const auto& word : corpus) {
@@ -330,6 +340,50 @@ int main(int argc, const char* argv[]) {
                 std::fputc('\n', pf);
             }
             std::fclose(pf);
+        }
+        if (!byte_marginals.empty() || !mea_decode.empty()) {   // per-byte state posteriors and the MEA decode at the final x
+            if (!have_fsa)
+                throw MyError(byte_marginals.empty() ? "-md" : "-bm", " needs an automaton and a corpus (-a / -c): matrix-file mode has no trellis");
+            const size_t n = recognized_strings.size();
+            size_t n_bytes = 0;
+            for (const auto& w : recognized_strings) n_bytes += w.size();
+            const bool decode = !mea_decode.empty();
+            int64_t n_entries = 0, n_path_entries = 0;
+            std::vector<double> logq(n + 1), boundary(n_bytes + 1), score(n + 1), logw(n + 1);
+            learner.ByteMarginals(decode, logq.data(), boundary.data(), score.data(), logw.data(), &n_entries, &n_path_entries);
+            if (!byte_marginals.empty()) {
+                std::vector<int64_t> mrow(n_bytes + 1);
+                std::vector<int32_t> midx(size_t(n_entries) + 1);
+                std::vector<double> mval(size_t(n_entries) + 1);
+                learner.ByteMarginalsGet(mrow.data(), midx.data(), mval.data());
+                const FlatModel flat(fsa);   // state ids in the device's numbering -> names
+                FILE* mf = std::fopen(byte_marginals.c_str(), "w");
+                if (!mf) throw MyError("Unable to open \"", byte_marginals, "\" for writing!");
+                size_t b = 0;
+                for (size_t s = 0; s < n; ++s) {
+                    std::fprintf(mf, "%s\t%.17g", recognized_strings[s].c_str(), logq[s]);
+                    for (size_t i = 0; i < recognized_strings[s].size(); ++i, ++b) {
+                        std::fprintf(mf, "\t%.17g\t", boundary[b]);
+                        for (int64_t q = mrow[b]; q < mrow[b + 1]; ++q)
+                            std::fprintf(mf, q > mrow[b] ? ",%s:%.17g" : "%s:%.17g", flat.state_names[size_t(midx[size_t(q)])], mval[size_t(q)]);
+                    }
+                    std::fputc('\n', mf);
+                }
+                std::fclose(mf);
+            }
+            if (decode) {
+                std::vector<int64_t> prow(n + 1);
+                std::vector<int32_t> pidx(size_t(n_path_entries) + 1);
+                learner.ByteMarginalsPathGet(prow.data(), pidx.data());
+                FILE* df = std::fopen(mea_decode.c_str(), "w");
+                if (!df) throw MyError("Unable to open \"", mea_decode, "\" for writing!");
+                for (size_t s = 0; s < n; ++s) {
+                    std::fprintf(df, "%s\t%.17g\t%.15g\t", recognized_strings[s].c_str(), score[s], logw[s]);
+                    for (int64_t q = prow[s]; q < prow[s + 1]; ++q) std::fprintf(df, q > prow[s] ? " %d" : "%d", pidx[size_t(q)]);
+                    std::fputc('\n', df);
+                }
+                std::fclose(df);
+            }
         }
         if (evaluate) {
             const auto results = learner.GetOptimizationResult(print);

@@ -139,6 +139,11 @@ std::string compile_trellis_model(const wfsa_model_desc& d, TrellisModel& out) {
     out.n_params = d.n_params;
     out.n_nodes = int32_t(n_nodes);
     out.start = d.start;
+    out.n_states = N;
+    out.owner.resize(size_t(n_nodes));
+    for (int32_t s = 0; s < N; ++s) out.owner[size_t(s)] = s;
+    for (int32_t e = 0; e < n_em; ++e)
+        for (int32_t k = 1; chain_base[e] >= 0 && k < d.em_len[e]; ++k) out.owner[size_t(chain_base[e] + k - 1)] = em_owner[e];
     out.o_ptr.assign(size_t(n_nodes) + 1, 0);
     out.x_ptr.assign(size_t(n_nodes) + 1, 0);
     out.node_end_count.assign(size_t(n_nodes), 0.0);

@@ -43,6 +43,10 @@ struct TrellisModel {
     std::vector<int32_t> x_pptr;   // [X+1]
     std::vector<int32_t> x_pidx;
     std::vector<double> node_end_count;  // [n_nodes] number of end edges
+    // the Fsa state every node belongs to: a state itself, a chain node the
+    // state that owns the emission it spells (nodes below n_states are states)
+    int32_t n_states = 0;
+    std::vector<int32_t> owner;    // [n_nodes]
 };
 
 // Returns an empty string on success, otherwise the reason the model was

@@ -40,6 +40,7 @@
 #include "fb_kernels.hpp"
 #include "decode.hpp"
 #include "sample.hpp"
+#include "marginals.hpp"
 #include "posterior.hpp"
 #include "trellis_model.hpp"
 
@@ -465,6 +466,22 @@ struct wfsa_dev {
     std::vector<int64_t> pc_crow;
     std::vector<int32_t> pc_cidx;
     std::vector<double> pc_cval;
+    // Per-byte state posteriors and the MEA decode (wfsa_dev_byte_marginals;
+    // marginals.hpp): a fifth buffer set, plus the stored rows, the gamma rows,
+    // the model's grouping tables, the corpus' base offsets, the dense state sums
+    // and what the kernels report -- and its last result for _get
+    DecodeBufs bm;
+    wfsa::MarginalTables bm_tab;        // host copy: g_ptr / g_state turn a group into a state id
+    DevBuf<int32_t> bm_ord, bm_seg, bm_grp;
+    DevBuf<int64_t> bm_base;            // [total_sym + 1], valid while bm_base_ok
+    bool bm_base_ok = false;            // computed for the loaded model and corpus
+    int64_t bm_words = 0;               // state-sum words of the loaded corpus (bm_base's last entry)
+    DevBuf<double> bm_hist, bm_logq, bm_bound, bm_score;
+    DevBuf<unsigned long long> bm_gamma, bm_mass;
+    bool bm_has_path = false;           // the last call decoded
+    std::vector<int64_t> bm_mrow, bm_prow;
+    std::vector<int32_t> bm_midx, bm_pidx;
+    std::vector<double> bm_mval;
     std::vector<int64_t> bp_prow;
     std::vector<int32_t> bp_pidx;
     std::vector<int64_t> kb_srow, kb_prow;
@@ -3008,7 +3025,10 @@ void drop_graph(wfsa_dev* ctx) {
 }
 
 // a load ends the decode results held for _get
-void invalidate_decodes(wfsa_dev* ctx) { ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = ctx->pc.valid = false; }
+void invalidate_decodes(wfsa_dev* ctx) {
+    ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = ctx->pc.valid = ctx->bm.valid = false;
+    ctx->bm_base_ok = false;   // (the state sums' addresses belong to one model and one corpus)
+}
 
 // weights in / results out, sized by n_params
 int alloc_param_buffers(wfsa_dev* ctx) {
@@ -3156,7 +3176,7 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     if (ctx->flag) (void)hipHostFree(ctx->flag);
     for (hipEvent_t ev : {ctx->ev0, ctx->ev1})
         if (ev) (void)hipEventDestroy(ev);
-    for (DecodeBufs* d : {&ctx->bp, &ctx->kb, &ctx->sp, &ctx->pc})
+    for (DecodeBufs* d : {&ctx->bp, &ctx->kb, &ctx->sp, &ctx->pc, &ctx->bm})
         for (hipEvent_t ev : {d->ev0, d->ev1})
             if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
@@ -3249,6 +3269,13 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
         ctx->max_dst = 1;
         for (int c = 0; c < 256; ++c) ctx->max_dst = std::max(ctx->max_dst, cptr[size_t(c) + 1] - cptr[size_t(c)]);
         ctx->n_in_edges = int64_t(esrc.size());
+        {   // byte_marginals: every byte's destination slots grouped by owner state
+            ctx->bm_tab = wfsa::build_marginal_tables(cptr, dst, tm.owner);
+            const wfsa::MarginalTables& mt = ctx->bm_tab;
+            HIP_TRY(ctx->bm_ord.upload(mt.ord.data(), mt.ord.size(), s));
+            HIP_TRY(ctx->bm_seg.upload(mt.seg.data(), mt.seg.size(), s));
+            HIP_TRY(ctx->bm_grp.upload(mt.grp.data(), mt.grp.size(), s));
+        }
         if (dst.empty()) dst.push_back(0);
         if (esrc.empty()) { esrc.push_back(0); eg.push_back(0); }
         HIP_TRY(ctx->w_cptr.upload(cptr.data(), cptr.size(), s));
@@ -4971,6 +4998,197 @@ int wfsa_dev_posterior_counts_get(wfsa_dev* ctx, int64_t* crow, int32_t* cidx, d
     if (crow) std::memcpy(crow, ctx->pc_crow.data(), ctx->pc_crow.size() * sizeof(int64_t));
     if (cidx && !ctx->pc_cidx.empty()) std::memcpy(cidx, ctx->pc_cidx.data(), ctx->pc_cidx.size() * sizeof(int32_t));
     if (cval && !ctx->pc_cval.empty()) std::memcpy(cval, ctx->pc_cval.data(), ctx->pc_cval.size() * sizeof(double));
+    return WFSA_OK;
+}
+
+// Per-byte state posteriors and the MEA decode (marginals.hpp): the sampler's
+// checks and waves in flight and buffers of its own (the context's `bm`).  The
+// state sums come back dense, at addresses fixed by the corpus; the host
+// compacts them into rows of (state id, mass).
+int wfsa_dev_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t decode, double* logq, double* boundary, double* score,
+                            double* path_logw, int64_t* n_entries, int64_t* n_path_entries) {
+    const char* name = "byte_marginals";
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to walk", name);
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (ctx->dense)
+        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to take its marginals", name);
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    const bool dec = decode != 0;
+    DecodeBufs& d = ctx->bm;
+    d.valid = false;
+    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end, T = ctx->total_sym;
+    const int64_t wave_bytes = wfsa::marginal_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst, dec);
+    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
+    if (fit < 1)
+        return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations) exceeds the budget", name,
+                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst);
+    hipStream_t s = ctx->stream;
+    const wfsa::MarginalTables& mt = ctx->bm_tab;
+    if (!ctx->bm_base_ok) {   // once per loaded corpus: where every byte's state sums start
+        std::vector<uint8_t> sym(size_t(std::max<int64_t>(T, 1)));
+        HIP_TRY(ctx->sym.download(sym.data(), size_t(T), s));
+        HIP_TRY(hipStreamSynchronize(s));
+        std::vector<int64_t> base(size_t(T) + 1, 0);
+        for (int64_t b = 0; b < T; ++b) base[size_t(b) + 1] = base[size_t(b)] + mt.n_groups(sym[size_t(b)]);
+        HIP_TRY(ctx->bm_base.upload(base.data(), base.size(), s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ctx->bm_words = base[size_t(T)];
+        ctx->bm_base_ok = true;
+    }
+    const int64_t words = ctx->bm_words;
+    constexpr int64_t kMassBudget = int64_t(4) << 30;
+    if (words * 8 > kMassBudget)
+        return fail(WFSA_ERR_CAPACITY, "%s: the state sums take %lld bytes (%lld corpus bytes), over the %lld-byte budget", name,
+                    (long long)(words * 8), (long long)T, (long long)kMassBudget);
+    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
+    int64_t max_waves = 16 * int64_t(ctx->n_cu);
+    if (const char* e = std::getenv("WFSA_MARGINAL_WAVES")) max_waves = std::max<int64_t>(1, std::min<int64_t>(max_waves, std::atoll(e)));
+    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({max_waves, fit, S}));
+    const int grid = int(std::max<int64_t>(1, waves / wpb));
+    const int64_t n_waves = int64_t(grid) * wpb;
+    if (!d.ev0) {
+        HIP_TRY(hipEventCreate(&d.ev0));
+        HIP_TRY(hipEventCreate(&d.ev1));
+    }
+    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
+    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    const int64_t hist = int64_t(std::max(ctx->max_len, 1)) * int64_t(std::max(ctx->max_dst, 1));
+    const size_t n_path = size_t(T + S);
+    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
+    HIP_TRY(d.lw.alloc(size_t(E + X)));
+    HIP_TRY(d.score.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(ctx->bm_hist.alloc(size_t(n_waves * hist)));
+    HIP_TRY(ctx->bm_gamma.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(d.ctr.alloc(1));
+    HIP_TRY(ctx->bm_mass.alloc(size_t(words)));
+    HIP_TRY(ctx->bm_logq.alloc(size_t(S)));
+    HIP_TRY(ctx->bm_bound.alloc(size_t(T)));
+    if (dec) {
+        HIP_TRY(d.back.alloc(size_t(n_waves * hist)));
+        HIP_TRY(d.best.alloc(size_t(S)));
+        HIP_TRY(d.path.alloc(n_path));
+        HIP_TRY(ctx->bm_score.alloc(size_t(S)));
+    }
+    wfsa::MarginalArgs a{};
+    a.d.w.c_ptr = ctx->w_cptr.ptr;
+    a.d.w.dst = ctx->w_dst.ptr;
+    a.d.w.e_ptr = ctx->w_eptr.ptr;
+    a.d.w.e_src = ctx->w_esrc.ptr;
+    a.d.w.e_g = ctx->w_eg.ptr;
+    a.d.x_ptr = ctx->x_ptr.ptr;
+    a.d.pptr = ctx->pptr.ptr;
+    a.d.pidx = ctx->pidx.ptr;
+    a.d.n_nodes = ctx->n_nodes;
+    a.d.start = ctx->start;
+    a.d.n_edges = int32_t(E);
+    a.d.n_end = int32_t(X);
+    a.d.sym = ctx->sym.ptr;
+    a.d.off = ctx->off.ptr;
+    a.d.n_strings = int32_t(S);
+    a.d.max_len = ctx->max_len;
+    a.d.max_dst = ctx->max_dst;
+    a.d.k = 1;
+    a.d.wt = d.w.ptr;
+    a.d.lw = d.lw.ptr;
+    a.d.score = d.score.ptr;
+    a.d.back = dec ? d.back.ptr : nullptr;
+    a.d.ctr = d.ctr.ptr;
+    a.d.best = dec ? d.best.ptr : nullptr;
+    a.d.path = dec ? d.path.ptr : nullptr;
+    a.hist = ctx->bm_hist.ptr;
+    a.gamma = ctx->bm_gamma.ptr;
+    a.n_states = ctx->h_tm->n_states;
+    a.ord = ctx->bm_ord.ptr;
+    a.seg = ctx->bm_seg.ptr;
+    a.grp = ctx->bm_grp.ptr;
+    a.base = ctx->bm_base.ptr;
+    a.mass = ctx->bm_mass.ptr;
+    a.logq = ctx->bm_logq.ptr;
+    a.boundary = ctx->bm_bound.ptr;
+    a.mea_score = dec ? ctx->bm_score.ptr : nullptr;
+    HIP_TRY(hipEventRecord(d.ev0, s));
+    HIP_TRY(wfsa::launch_marginal_rows(a, words, grid, wpb, s));
+    if (dec) HIP_TRY(wfsa::launch_marginal_decode(a, grid, wpb, s));
+    HIP_TRY(hipEventRecord(d.ev1, s));
+    std::vector<double> lq(size_t(S), 0.0), bound(size_t(T), 0.0), sc, plw;
+    std::vector<unsigned long long> mass(static_cast<size_t>(words));
+    std::vector<int64_t> off(size_t(S) + 1), base(size_t(T) + 1);
+    std::vector<uint8_t> sym(size_t(std::max<int64_t>(T, 1)));
+    std::vector<int32_t> path;
+    HIP_TRY(ctx->bm_logq.download(lq.data(), size_t(S), s));
+    HIP_TRY(ctx->bm_bound.download(bound.data(), size_t(T), s));
+    HIP_TRY(ctx->bm_mass.download(mass.data(), size_t(words), s));
+    HIP_TRY(ctx->bm_base.download(base.data(), size_t(T) + 1, s));
+    HIP_TRY(ctx->sym.download(sym.data(), size_t(T), s));
+    HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
+    if (dec) {
+        sc.resize(size_t(S));
+        plw.resize(size_t(S));
+        path.resize(n_path);
+        HIP_TRY(ctx->bm_score.download(sc.data(), size_t(S), s));
+        HIP_TRY(d.best.download(plw.data(), size_t(S), s));
+        HIP_TRY(d.path.download(path.data(), n_path, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    ctx->stats.byte_marginal_ms = double(ms);
+    // the rows: per corpus byte the groups whose fixed-point sum is not 0, as state ids (ascending: the groups ascend by owner)
+    ctx->bm_mrow.assign(size_t(T) + 1, 0);
+    ctx->bm_midx.clear();
+    ctx->bm_mval.clear();
+    const size_t listed = size_t(std::count_if(mass.begin(), mass.end(), [](unsigned long long v) { return v != 0ull; }));
+    ctx->bm_midx.reserve(listed);
+    ctx->bm_mval.reserve(listed);
+    for (int64_t b = 0; b < T; ++b) {
+        const int c = sym[size_t(b)];
+        const int32_t* st = mt.g_state.data() + mt.g_ptr[size_t(c)];
+        const unsigned long long* wd = mass.data() + base[size_t(b)];
+        for (int32_t g = 0; g < mt.n_groups(c); ++g)
+            if (wd[g] != 0ull) {
+                ctx->bm_midx.push_back(st[g]);
+                ctx->bm_mval.push_back(std::ldexp(double(wd[g]), -wfsa::kMarginalFrac));
+            }
+        ctx->bm_mrow[size_t(b) + 1] = int64_t(ctx->bm_midx.size());
+    }
+    ctx->bm_prow.assign(size_t(S) + 1, 0);
+    ctx->bm_pidx.clear();
+    if (dec)
+        for (int64_t i = 0; i < S; ++i) {
+            const int32_t* pe = path.data() + off[size_t(i)] + i;
+            if (pe[0] >= 0)
+                if (int rc = expand_path(ctx, name, i, -1, pe, off[size_t(i) + 1] - off[size_t(i)], ctx->bm_pidx)) return rc;
+            ctx->bm_prow[size_t(i) + 1] = int64_t(ctx->bm_pidx.size());
+        }
+    ctx->bm_has_path = dec;
+    d.valid = true;
+    if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
+    if (boundary && T > 0) std::memcpy(boundary, bound.data(), size_t(T) * sizeof(double));
+    if (dec && score && S > 0) std::memcpy(score, sc.data(), size_t(S) * sizeof(double));
+    if (dec && path_logw && S > 0) std::memcpy(path_logw, plw.data(), size_t(S) * sizeof(double));
+    if (n_entries) *n_entries = int64_t(ctx->bm_midx.size());
+    if (n_path_entries) *n_path_entries = int64_t(ctx->bm_pidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow, int32_t* midx, double* mval) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->bm.valid) return fail(WFSA_ERR_ARG, "byte_marginals_get: no wfsa_dev_byte_marginals result since the last load");
+    if (mrow) std::memcpy(mrow, ctx->bm_mrow.data(), ctx->bm_mrow.size() * sizeof(int64_t));
+    if (midx && !ctx->bm_midx.empty()) std::memcpy(midx, ctx->bm_midx.data(), ctx->bm_midx.size() * sizeof(int32_t));
+    if (mval && !ctx->bm_mval.empty()) std::memcpy(mval, ctx->bm_mval.data(), ctx->bm_mval.size() * sizeof(double));
+    return WFSA_OK;
+}
+
+int wfsa_dev_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->bm.valid) return fail(WFSA_ERR_ARG, "byte_marginals_path_get: no wfsa_dev_byte_marginals result since the last load");
+    if (!ctx->bm_has_path) return fail(WFSA_ERR_ARG, "byte_marginals_path_get: the last wfsa_dev_byte_marginals call had decode = 0");
+    if (prow) std::memcpy(prow, ctx->bm_prow.data(), ctx->bm_prow.size() * sizeof(int64_t));
+    if (pidx && !ctx->bm_pidx.empty()) std::memcpy(pidx, ctx->bm_pidx.data(), ctx->bm_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
 

@@ -115,6 +115,15 @@ class Fsa:
     def param_names(self):
         return [self.param_name(j) for j in range(self.counts()["parameters"])]
 
+    def state_name(self, state):
+        s = C.c_char_p()
+        check_host(load().wfsa_fsa_state_name(self._h, state, C.byref(s)))
+        return s.value.decode("latin-1")
+
+    def state_names(self):
+        """state id (desc() numbering) -> name"""
+        return [self.state_name(u) for u in range(self.counts()["states"])]
+
 
 class Corpus:
     """The string store (inc/Corpus.h): .corpus reader; weights as read."""
@@ -352,6 +361,21 @@ class QuasiNewtonLearner:
         check_host(load().wfsa_learner_posterior_counts_get(self._h, _ptr(crow), _ptr(cidx), _ptr(cval)))
         return crow, cidx[:m.value], cval[:m.value], logq, ent
 
+    def ByteMarginals(self, decode=False):
+        """per-byte state posteriors at the current x over the local recognized
+        strings, their bytes back to back in p()'s order: (mrow, midx, mval,
+        boundary, logq) -- byte b owns the ascending state ids
+        midx[mrow[b]:mrow[b + 1]] (Fsa.state_names() names them) with their
+        posterior masses mval, boundary[b] is the probability that an emission
+        ends with it and logq[s] the string's log q.  With decode=True also
+        (score, path_logw, prow, pidx): the max-expected-accuracy path of every
+        string in BestPaths' layout, its expected number of correctly
+        attributed bytes and its log weight"""
+        n = self.info()["n_local_strings"]
+        nb = int(self.stats()["total_symbols"])
+        return _byte_marginals(load().wfsa_learner_byte_marginals, load().wfsa_learner_byte_marginals_get,
+                               load().wfsa_learner_byte_marginals_path_get, check_host, (self._h,), n, nb, decode)
+
     def trimmed_index(self):
         a = np.zeros(self.info()["n_full"], dtype=np.int32)
         check_host(load().wfsa_learner_trimmed_index(self._h, _ptr(a)))
@@ -451,6 +475,27 @@ def torch_allreduce(arr, op):
     t = torch.from_numpy(arr)
     limit = float(os.environ.get("WFSA_COMM_TIMEOUT_S", "300"))
     dist.all_reduce(t, op=red, async_op=True).wait(timeout=datetime.timedelta(seconds=limit))
+
+
+def _byte_marginals(call, get, path_get, check, head, n_strings, n_bytes, decode):
+    """the byte_marginals call sequence, shared by Device and the learners"""
+    m, mp = C.c_int64(), C.c_int64()
+    logq = np.zeros(n_strings, dtype=np.float64)
+    boundary = np.zeros(n_bytes, dtype=np.float64)
+    score = np.zeros(n_strings, dtype=np.float64) if decode else None
+    plw = np.zeros(n_strings, dtype=np.float64) if decode else None
+    check(call(*head, 1 if decode else 0, _ptr(logq), _ptr(boundary), _ptr(score), _ptr(plw), C.byref(m), C.byref(mp)))
+    mrow = np.zeros(n_bytes + 1, dtype=np.int64)
+    midx = np.zeros(max(m.value, 1), dtype=np.int32)
+    mval = np.zeros(max(m.value, 1), dtype=np.float64)
+    check(get(head[0], _ptr(mrow), _ptr(midx), _ptr(mval)))
+    out = (mrow, midx[:m.value], mval[:m.value], boundary, logq)
+    if not decode:
+        return out
+    prow = np.zeros(n_strings + 1, dtype=np.int64)
+    pidx = np.zeros(max(mp.value, 1), dtype=np.int32)
+    check(path_get(head[0], _ptr(prow), _ptr(pidx)))
+    return out + (score, plw, prow, pidx[:mp.value])
 
 
 class Device:
@@ -656,6 +701,27 @@ class Device:
         cval = np.zeros(max(m.value, 1), dtype=np.float64)
         check_dev(load().wfsa_dev_posterior_counts_get(self._h, _ptr(crow), _ptr(cidx), _ptr(cval)))
         return crow, cidx[:m.value], cval[:m.value], logq, ent
+
+    def byte_marginals(self, w_full, decode=False):
+        """per-byte state posteriors at w_full: (mrow, midx, mval, boundary, logq)
+        -- corpus byte b = off[s] + i - 1 owns the ascending Fsa state ids
+        midx[mrow[b]:mrow[b + 1]], each with mval > 0, the posterior probability
+        that byte i of s lies inside an emission of that state (they sum to 1);
+        boundary[b] is the probability that an emission ends with the byte and
+        logq[s] the string's log q (posterior_counts' bytes).  With decode=True
+        also (score, path_logw, prow, pidx): the accepting path of finite weight
+        that maximises the expected number of correctly attributed bytes
+        (score), its log weight and its Fsa parameter ids
+        pidx[prow[s]:prow[s + 1]] in path order.  A string without an accepting
+        path of finite weight owns nothing (logq -inf, boundary NaN, score NaN,
+        path_logw -inf).  The same weights give the same bytes on every call"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        off = getattr(self, "_off", None)
+        return _byte_marginals(load().wfsa_dev_byte_marginals, load().wfsa_dev_byte_marginals_get,
+                               load().wfsa_dev_byte_marginals_path_get, check_dev, (self._h, _ptr(w)), self.n_strings,
+                               int(off[-1]) if off is not None and len(off) else 0, decode)
 
     def comm_init(self, nranks, rank, unique_id):
         buf = (C.c_uint8 * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))

@@ -52,7 +52,7 @@ class DevStats(C.Structure):
         ("stream_block", i32), ("stream_w_lds", i32), ("stream_wide", i32), ("stream_multi", i32),
         ("stream_delta", i32), ("bubbles_fused", i32), ("grad_tables", i32), ("wave_lgrad", i32),
         ("ll_dot_launches", i64), ("best_path_ms", dbl), ("kbest_path_ms", dbl),
-        ("sample_path_ms", dbl), ("posterior_count_ms", dbl),
+        ("sample_path_ms", dbl), ("posterior_count_ms", dbl), ("byte_marginal_ms", dbl),
     ]
 
 
@@ -89,6 +89,9 @@ _SIGS = {
     "wfsa_dev_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_posterior_counts": (C.c_int, [vp, vp, vp, vp, P(i64)]),
     "wfsa_dev_posterior_counts_get": (C.c_int, [vp, vp, vp, vp]),
+    "wfsa_dev_byte_marginals": (C.c_int, [vp, vp, C.c_int32, vp, vp, vp, vp, P(i64), P(i64)]),
+    "wfsa_dev_byte_marginals_get": (C.c_int, [vp, vp, vp, vp]),
+    "wfsa_dev_byte_marginals_path_get": (C.c_int, [vp, vp, vp]),
     "wfsa_dev_sample_uniforms": (C.c_int, [C.c_int, C.c_uint64, i64, C.c_int32, C.c_int32, vp]),
     "wfsa_dev_sym_factor": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp]),
     "wfsa_dev_sym_solve": (C.c_int, [vp, vp]),
@@ -123,6 +126,7 @@ _SIGS = {
     "wfsa_fsa_free": (None, [vp]),
     "wfsa_fsa_desc": (C.c_int, [vp, P(ModelDesc)]),
     "wfsa_fsa_counts": (C.c_int, [vp, vp]),
+    "wfsa_fsa_state_name": (C.c_int, [vp, i32, P(C.c_char_p)]),
     "wfsa_fsa_param_name": (C.c_int, [vp, i32, P(C.c_char_p), P(i32), P(C.c_char_p)]),
     "wfsa_corpus_read_text": (C.c_int, [C.c_char_p, P(vp)]),
     "wfsa_corpus_read_file": (C.c_int, [C.c_char_p, P(vp)]),
@@ -155,6 +159,9 @@ _SIGS = {
     "wfsa_learner_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_learner_posterior_counts": (C.c_int, [vp, vp, vp, P(i64)]),
     "wfsa_learner_posterior_counts_get": (C.c_int, [vp, vp, vp, vp]),
+    "wfsa_learner_byte_marginals": (C.c_int, [vp, C.c_int32, vp, vp, vp, vp, P(i64), P(i64)]),
+    "wfsa_learner_byte_marginals_get": (C.c_int, [vp, vp, vp, vp]),
+    "wfsa_learner_byte_marginals_path_get": (C.c_int, [vp, vp, vp]),
     "wfsa_learner_trimmed_index": (C.c_int, [vp, vp]),
     "wfsa_learner_path_counts": (C.c_int, [vp, vp, vp]),
     "wfsa_learner_renormalize": (C.c_int, [vp]),
