@@ -131,6 +131,10 @@ typedef struct {
     double sample_path_ms;     /* last wfsa_dev_sample_paths call: device time of its kernels */
     double posterior_count_ms; /* last wfsa_dev_posterior_counts call: device time of its kernels */
     double byte_marginal_ms;   /* last wfsa_dev_byte_marginals call: device time of its kernels */
+    int64_t shaped_bubbles;    /* small bubbles whose structure has compiled-in sweeps (WFSA_BUBBLE_SHAPES=0: none) */
+    int64_t mixed_shape_waves; /* small-bubble waves whose lanes carry more than one structure id (several sweep turns) */
+    int64_t small_bubbles_a;   /* small bubbles of class A (<= 4 nodes and edges), one lane each */
+    int64_t small_bubbles_b;   /* small bubbles of class B (<= 8 nodes and edges); n_bubbles counts the big ones too */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */

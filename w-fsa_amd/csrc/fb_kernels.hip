@@ -2085,8 +2085,9 @@ __device__ __forceinline__ void edge_weight_slice(const CompiledArgs& a, int bid
 //
 // Small bubbles, one lane each: the bubble's quads are loaded in one round
 // (structure-of-arrays, coalesced), the weights gathered in a second, and
-// alpha/beta of its at most 8 nodes live in registers, addressed through a
-// tree of selects on the node id.
+// alpha/beta of its at most 8 nodes live in registers: plain ones in the
+// sweeps compiled for a listed structure (shaped_sweeps), else addressed
+// through a tree of selects on the node id.
 // r[i] for i < 8 as a tree of selects on the bits of i (a compare chain is
 // re-formed into an indexed scratch load by the compiler)
 template <int N>
@@ -2152,9 +2153,6 @@ __device__ __forceinline__ double group_sum(double v, int k, int kmax) {
 #ifndef WFSA_BIG_PRIO
 #define WFSA_BIG_PRIO 3
 #endif
-#ifndef WFSA_UNI_BUBBLES   // (variant builds: the uniform-structure path of small bubbles)
-#define WFSA_UNI_BUBBLES 0
-#endif
 // (tr: timing experiments only, stamps 8..11 of the wave's trace row)
 #define WFSA_BSTAMP(k)                                                   \
     if (tr) {                                                            \
@@ -2162,28 +2160,28 @@ __device__ __forceinline__ double group_sum(double v, int k, int kmax) {
         if (lane_id() == 0) tr[k] = __builtin_amdgcn_s_memrealtime();    \
     }
 // The rmin column's (min, x) forward over a small bubble's edges (weights
-// ew, nodes sd, header h), log(min path / Z).  The node vector is indexed
-// register-direct: by the wave's shared structure (uni), else by a
-// waterfall over the wave's bubble shapes (sorted by shape: few) -- the
-// first pending lane's structure, read into scalars, runs for every lane and
-// the lanes of that shape keep the result (per-lane node indices put the
-// vector in scratch memory).  min(a, b) x w = min(a x w, b x w) exactly, so
-// any topological order gives the same bits.
+// ew, nodes sd, header h): the min path's weight (the column adds
+// log(min path / Z)).  The node vector is indexed
+// register-direct by a waterfall over the wave's bubble shapes (sorted by
+// shape: few) -- the first pending lane's structure, read into scalars, runs
+// for every lane and the lanes of that shape keep the result (per-lane node
+// indices put the vector in scratch memory).  min(a, b) x w = min(a x w, b x w)
+// exactly, so any topological order gives the same bits.
 template <int N, int RE>
-__device__ __forceinline__ double min_path_log(const double (&ew)[RE], const int (&sd)[RE], int h, bool uni, double Z) {
-    double rv = 0.0;
+__device__ __forceinline__ double min_path(const double (&ew)[RE], const int (&sd)[RE], int h) {
+    double rv = 1.0;
     bool pending = true;
     while (true) {
         const unsigned long long m = __ballot(pending);
         if (m == 0ull) break;
-        const int lead = uni ? 0 : __ffsll(m) - 1;
+        const int lead = __ffsll(m) - 1;
         const int hu = __builtin_amdgcn_readlane(h, lead);
-        bool mine = pending && (uni || h == hu);
+        bool mine = pending && h == hu;
         int su[RE];
 #pragma unroll
         for (int e = 0; e < RE; ++e) {
             su[e] = __builtin_amdgcn_readlane(sd[e], lead);
-            mine = mine && (uni || sd[e] == su[e]);
+            mine = mine && sd[e] == su[e];
         }
         const int eu = hu >> 16, nu = hu & 0xffff;
         double B[N];
@@ -2196,11 +2194,117 @@ __device__ __forceinline__ double min_path_log(const double (&ew)[RE], const int
                 B[su[e] >> 16] = ew[e] > 0.0 ? fmin(B[su[e] >> 16], v) : B[su[e] >> 16];
             }
         if (mine) {
-            rv = log(B[nu - 1] / Z);
+            rv = B[nu - 1];
             pending = false;
         }
     }
     return rv;
+}
+
+// The two sweeps of a small bubble, per lane: Z, scale = -p / Z and c[e], edge
+// e's contribution before its group's sum.  Both forms do the same operations
+// in the same order (fp contract off), so they give the same bits.
+// c may be ew itself: an edge's weight is read for the last time where its
+// contribution is written.
+// Any structure: alpha / beta addressed per lane through the select trees.
+template <int N, int RE>
+__device__ __forceinline__ void generic_sweeps(const double (&ew)[RE], const int (&sd)[RE], int hdr, double p, double& Z,
+                                               double& scale, double (&c)[RE]) {
+#pragma clang fp contract(off)
+    const int nodes = hdr & 0xffff, edges = hdr >> 16;
+    double A[N], B[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        A[k] = k == 0 ? 1.0 : 0.0;
+        B[k] = 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < RE; ++e)
+        if (e < edges) reg_add(A, sd[e] >> 16, reg_get(A, sd[e] & 0xffff) * ew[e]);
+    Z = reg_get(A, nodes - 1);
+    scale = -p / Z;
+    reg_add(B, nodes - 1, 1.0);
+#pragma unroll
+    for (int e = RE - 1; e >= 0; --e)
+        if (e < edges) {
+            const int src = sd[e] & 0xffff;
+            const double bb = ew[e] * reg_get(B, sd[e] >> 16);
+            reg_add(B, src, bb);
+            c[e] = reg_get(A, src) * bb * scale;
+        }
+}
+// Structure S of the class's list (kBubbleShapesA / B): the node indices and
+// the edge count are compile-time, alpha / beta plain registers.
+template <int I>
+struct IntC {
+    static constexpr int value = I;
+};
+template <int I, int END, class F>
+__device__ __forceinline__ void static_for(F&& f) {   // f(IntC<I>), ..., f(IntC<END - 1>)
+    if constexpr (I < END) {
+        f(IntC<I>{});
+        static_for<I + 1, END>(f);
+    }
+}
+template <int I, class F>
+__device__ __forceinline__ void static_for_down(F&& f) {   // f(IntC<I - 1>), ..., f(IntC<0>)
+    if constexpr (I > 0) {
+        f(IntC<I - 1>{});
+        static_for_down<I - 1>(f);
+    }
+}
+template <int RE, int S>
+constexpr BubbleShape bubble_shape() {
+    if constexpr (RE == 4) return kBubbleShapesA[S];
+    else return kBubbleShapesB[S];
+}
+template <int N, int RE, int S>
+__device__ __forceinline__ void shaped_sweeps(const double (&ew)[RE], double p, double& Z, double& scale, double (&c)[RE]) {
+#pragma clang fp contract(off)
+    constexpr BubbleShape sh = bubble_shape<RE, S>();
+    static_assert(sh.nodes >= 1 && sh.nodes <= N && sh.edges <= RE, "the structure fits its class");
+    double A[N], B[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        A[k] = k == 0 ? 1.0 : 0.0;
+        B[k] = 0.0;
+    }
+    static_for<0, sh.edges>([&](auto ic) {
+#pragma clang fp contract(off)
+        constexpr int e = decltype(ic)::value, src = sh.sd[e] & 0xffff, dst = sh.sd[e] >> 16;
+        static_assert(src < sh.nodes && dst < sh.nodes, "the edge's nodes");
+        A[dst] = A[dst] + A[src] * ew[e];
+    });
+    Z = A[sh.nodes - 1];
+    scale = -p / Z;
+    B[sh.nodes - 1] = B[sh.nodes - 1] + 1.0;
+    static_for_down<sh.edges>([&](auto ic) {
+#pragma clang fp contract(off)
+        constexpr int e = decltype(ic)::value, src = sh.sd[e] & 0xffff, dst = sh.sd[e] >> 16;
+        const double bb = ew[e] * B[dst];
+        B[src] = B[src] + bb;
+        c[e] = A[src] * bb * scale;
+    });
+}
+// the sweeps of structure id su (wave-uniform: a scalar compare chain), 0 or
+// past the list: the generic ones
+template <int N, int RE, int S = 0>
+__device__ __forceinline__ void sweeps_of(int su, const double (&ew)[RE], const int (&sd)[RE], int hdr, double p, double& Z,
+                                          double& scale, double (&c)[RE]) {
+    // (the empty asm keeps each arm a block of its own: the arms are pure
+    // arithmetic, and the compiler otherwise runs all of them and selects --
+    // every structure's sweeps in every turn, their results spilled)
+    if constexpr (S < (RE == 4 ? kBubbleShapesNA : kBubbleShapesNB)) {
+        if (su == S + 1) {
+            asm volatile("");
+            shaped_sweeps<N, RE, S>(ew, p, Z, scale, c);
+        } else {
+            sweeps_of<N, RE, S + 1>(su, ew, sd, hdr, p, Z, scale, c);
+        }
+    } else {
+        asm volatile("");
+        generic_sweeps<N, RE>(ew, sd, hdr, p, Z, scale, c);
+    }
 }
 
 // rl (RMIN, optional): the folded rmin column's record of the bubble
@@ -2211,18 +2315,26 @@ __device__ __forceinline__ double min_path_log(const double (&ew)[RE], const int
 // LZ (bubble_kernel): a.logq is the per-bubble log Z array -- the value is
 // stored at the bubble's list position and logq_bubbles_kernel adds each
 // string's in bubble order -- instead of the strings' entries it is added to
-template <int N, int RE, bool RMIN = false, bool FOLD = false, bool LZ = false>
+// SHAPES (step_dot_kernel without the rmin column): the wave runs the sweeps
+// compiled for its lanes' structures, by the ids in the table headers (0: the
+// generic sweeps); without it every lane runs the generic sweeps (fbs_kernel's
+// many variants; the rmin variants: the (min, x) pass reads the weights after
+// the sweeps, and with the turns step_dot_kernel's spill 17 registers at
+// their 128; bubble_kernel: 131 VGPRs against 110, three waves per SIMD for
+// four, made the log q evaluation 1 us slower at c3)
+template <int N, int RE, bool RMIN = false, bool FOLD = false, bool LZ = false, bool SHAPES = false>
 __device__ __forceinline__ double small_bubble(const BubbleArgs& a, const int4* __restrict__ tbl, int n, int b,
                                                int pos, unsigned long long* tr = nullptr, const RminFold* rf = nullptr,
                                                RminLane* rl = nullptr) {
-#pragma clang fp contract(off)   // (both forms below: the same bits)
+#pragma clang fp contract(off)
+    static_assert(!(SHAPES && RMIN), "the per-structure sweeps leave no weights for the (min, x) pass");
     constexpr int NQ = 1 + RE / 2 + RE / 4;
     int4 q[NQ];
 #pragma unroll
     for (int k = 0; k < NQ; ++k) q[k] = tbl[size_t(k) * size_t(n) + size_t(b)];
     const int2 bk = rf ? rf->bk[pos] : make_int2(0, 0);   // (in flight with the quads)
     WFSA_BSTAMP(8)
-    const int nodes = q[0].x & 0xffff, edges = q[0].x >> 16;
+    const int hdr = q[0].x & ~kBubbleShapeMask, sid = (q[0].x & kBubbleShapeMask) >> kBubbleShapeShift;   // nodes | edges << 16
     const double p = __longlong_as_double((long long)(uint32_t(q[0].z)) | ((long long)(uint32_t(q[0].w)) << 32));
     int code[RE], sd[RE], slot[RE];
 #pragma unroll
@@ -2243,61 +2355,19 @@ __device__ __forceinline__ double small_bubble(const BubbleArgs& a, const int4* 
 #pragma unroll
     for (int e = 0; e < RE; ++e) ew[e] = (WFSA_KDBG(a.dbg) & 2) ? 1.0 + 1e-3 * code[e] : a.ewp[code[e]];   // padding edges carry the zero-slot code
     WFSA_BSTAMP(9)
-    double A[N], B[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        A[k] = k == 0 ? 1.0 : 0.0;
-        B[k] = 0.0;
-    }
-    // Bubbles are sorted by shape, so the lanes of a wave mostly share one
-    // structure (header and every edge's nodes): then the node indices are
-    // wave-uniform and address the registers directly (s_set_gpr_idx), else
-    // every access is a tree of selects (reg_get / reg_add)
-    bool same = q[0].x == __builtin_amdgcn_readfirstlane(q[0].x);
-#pragma unroll
-    for (int e = 0; e < RE; ++e) same = same && sd[e] == __builtin_amdgcn_readfirstlane(sd[e]);
-    const bool uni = WFSA_UNI_BUBBLES && __all(same);
-    if (uni) {
-        const int eu = __builtin_amdgcn_readfirstlane(edges);
-#pragma unroll
-        for (int e = 0; e < RE; ++e)
-            if (e < eu) {
-                const int s = __builtin_amdgcn_readfirstlane(sd[e]);
-                const double v = A[s & 0xffff] * ew[e];
-                A[s >> 16] = A[s >> 16] + v;
-            }
-    } else {
-#pragma unroll
-        for (int e = 0; e < RE; ++e)
-            if (e < edges) reg_add(A, sd[e] >> 16, reg_get(A, sd[e] & 0xffff) * ew[e]);
-    }
-    const double Z = uni ? A[__builtin_amdgcn_readfirstlane(nodes) - 1] : reg_get(A, nodes - 1);
-    const double scale = -p / Z;
-
-    WFSA_BSTAMP(10)
-    auto rmin_pass = [&]() {   // (the min path never exceeds Z)
-        const double rv = min_path_log<N, RE>(ew, sd, q[0].x, uni, Z);
-        if (a.rmin_sv) {
-            if (a.wt) store_wt(&a.rmin_sv[pos], rv);
-            else a.rmin_sv[pos] = rv;
-        } else {
-            global_add(&a.rmin_acc[q[0].y], rv);
-        }
-    };
-    if (RMIN && !FOLD && a.rmin_acc) rmin_pass();
-    if (uni) B[__builtin_amdgcn_readfirstlane(nodes) - 1] = 0.0 + 1.0;
-    else reg_add(B, nodes - 1, 1.0);
+    const int lane = lane_id();
+    int kl = 0, kmax = 0;
     // lanes of an aligned 2^k group sharing edge e's parameter (slot field
     // level k, layout_slots) sum their contributions by a butterfly -- every
     // lane of the group gets the same bits, in a fixed order -- and the
     // group's first lane stores the one slot; the partners of a grouped lane
     // are active (their edge e exists), the rest ignore what they read
-    int kl = 0, kmax = 0;   // (ballots: over the active lanes only -- this runs inside the class branch)
+    auto group_levels = [&]() {   // (ballots: over the active lanes only -- this runs inside the class branch)
 #pragma unroll
-    for (int e = 0; e < RE; ++e) kl = max(kl, slot[e] >= 0 ? (slot[e] >> 28) : 0);
+        for (int e = 0; e < RE; ++e) kl = max(kl, slot[e] >= 0 ? (slot[e] >> 28) : 0);
 #pragma unroll
-    for (int t = 1; t <= 6; ++t) kmax = __ballot(kl >= t) ? t : kmax;
-    const int lane = lane_id();
+        for (int t = 1; t <= 6; ++t) kmax = __ballot(kl >= t) ? t : kmax;
+    };
     auto contribute = [&](int e, double v) {   // edge e's slot (its group's sum, by the group's first lane)
         const int k = slot[e] >= 0 ? (slot[e] >> 28) : 0;
         v = group_sum(v, k, kmax);
@@ -2306,17 +2376,74 @@ __device__ __forceinline__ double small_bubble(const BubbleArgs& a, const int4* 
             else a.contrib[slot[e] & 0x0fffffff] = v;
         }
     };
-    if (uni) {
-        const int eu = __builtin_amdgcn_readfirstlane(edges);
+    double Z = 1.0, mp = 1.0;   // (mp: the rmin column's min path weight)
+    auto rmin_pass = [&]() {   // (the min path never exceeds Z)
+        const double rv = log(mp / Z);
+        if (a.rmin_sv) {
+            if (a.wt) store_wt(&a.rmin_sv[pos], rv);
+            else a.rmin_sv[pos] = rv;
+        } else {
+            global_add(&a.rmin_acc[q[0].y], rv);
+        }
+    };
+    if constexpr (SHAPES) {
+        // Phase 1, per lane: Z and the edges' contributions.  Bubbles are
+        // sorted by shape, so the lanes of a wave mostly share one structure:
+        // a waterfall over the wave's distinct structure ids -- the first
+        // pending lane's id, read into a scalar, selects the sweeps compiled
+        // for it and the lanes of that id run them; id 0 (not compiled in) is
+        // one more turn, on the select trees (reg_get / reg_add).
+        // Edge e's contribution takes the place of ew[e], which its lane's
+        // sweeps have read for the last time: across the turns the weights
+        // stay live for the other lanes, and eight more doubles beside them
+        // do not fit the 128 registers (an edge past the lane's last keeps
+        // its padding weight: no slot, never a grouped lane's partner)
+        double scale = 0.0;
+        bool pending = true;
+        while (true) {
+            const unsigned long long m = __ballot(pending);
+            if (m == 0ull) break;
+            const int su = __builtin_amdgcn_readlane(sid, __ffsll(m) - 1);
+            if (sid == su) {
+                // (the specialised sweeps depend on the weights alone, which
+                // do not change from turn to turn: passed through an empty
+                // asm here, or every structure's sweeps are hoisted out of
+                // the loop and run by every wave)
 #pragma unroll
-        for (int e = RE - 1; e >= 0; --e)
-            if (e < eu) {
-                const int s = __builtin_amdgcn_readfirstlane(sd[e]);
-                const double bb = ew[e] * B[s >> 16];
-                B[s & 0xffff] = B[s & 0xffff] + bb;
-                contribute(e, A[s & 0xffff] * bb * scale);
+                for (int e = 0; e < RE; ++e) asm volatile("" : "+v"(ew[e]));
+                sweeps_of<N, RE>(su, ew, sd, hdr, p, Z, scale, ew);
+                pending = false;
             }
+        }
+        WFSA_BSTAMP(10)
+        // Phase 2, all lanes together (a lane's butterfly partner shares its
+        // edge's parameter, not necessarily its structure), from the last
+        // edge down: the groups' sums and the slot stores
+        group_levels();
+#pragma unroll
+        for (int e = RE - 1; e >= 0; --e) contribute(e, ew[e]);
     } else {
+        // every lane on the select trees (reg_get / reg_add), an edge's
+        // contribution summed and stored as the backward sweep passes it
+        const int nodes = hdr & 0xffff, edges = hdr >> 16;
+        double A[N], B[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            A[k] = k == 0 ? 1.0 : 0.0;
+            B[k] = 0.0;
+        }
+#pragma unroll
+        for (int e = 0; e < RE; ++e)
+            if (e < edges) reg_add(A, sd[e] >> 16, reg_get(A, sd[e] & 0xffff) * ew[e]);
+        Z = reg_get(A, nodes - 1);
+        const double scale = -p / Z;
+        WFSA_BSTAMP(10)
+        if (RMIN && !FOLD && a.rmin_acc) {
+            mp = min_path<N, RE>(ew, sd, hdr);
+            rmin_pass();
+        }
+        reg_add(B, nodes - 1, 1.0);
+        group_levels();
 #pragma unroll
         for (int e = RE - 1; e >= 0; --e)
             if (e < edges) {
@@ -2334,7 +2461,8 @@ __device__ __forceinline__ double small_bubble(const BubbleArgs& a, const int4* 
         global_add(&a.logq[q[0].y], lz);
     }
     if (FOLD) {
-        const double rv = min_path_log<N, RE>(ew, sd, q[0].x, uni, Z);
+        mp = min_path<N, RE>(ew, sd, hdr);
+        const double rv = log(mp / Z);
         rl->rv = rv;
         rl->str = q[0].y;
         rl->k = bk.x;
@@ -3468,10 +3596,11 @@ __global__ __launch_bounds__(1024) void step_dot_kernel(CompiledArgs a) {
             const RminFold rf = WFSA_LATE_ARG(rf);
             const RminFold* rfp = RF ? &rf : nullptr;
             RminLane* rlp = RF ? &rm_lane : nullptr;
+            // (the structures' compiled sweeps: not beside the rmin column's registers, see small_bubble)
             if (b >= 0 && b < bub.n_small4)
-                ll_acc += small_bubble<4, 4, RMIN, RF>(bub, bub.sm4_tbl, bub.n_small4, b, b, btr, rfp, rlp);
+                ll_acc += small_bubble<4, 4, RMIN, RF, false, !RMIN>(bub, bub.sm4_tbl, bub.n_small4, b, b, btr, rfp, rlp);
             else if (b >= bub.n_small4)
-                ll_acc += small_bubble<8, 8, RMIN, RF>(bub, bub.sm_tbl, bub.n_small, b - bub.n_small4, b, btr, rfp, rlp);
+                ll_acc += small_bubble<8, 8, RMIN, RF, false, !RMIN>(bub, bub.sm_tbl, bub.n_small, b - bub.n_small4, b, btr, rfp, rlp);
             if (RF && b >= 0) {
                 rm_pos = int(b);
                 if (rm_lane.k == 1) min_pair(rm_cv, rm_ci, rm_lane.rv, double(rm_lane.str));

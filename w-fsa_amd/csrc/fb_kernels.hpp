@@ -571,6 +571,57 @@ __host__ __device__ inline int big_rank(int bid, int wib, int nblk, int wpb, int
     return r >= 2 * nblk - 1 - qw_waves ? r - qw_waves : r;
 }
 constexpr int kSmallBubbleQuads4 = 4;   // class A: <= 4 nodes, <= 4 edges (1 + 2 + 1 quads)
+// Small-bubble structures with sweeps compiled for them (small_bubble's
+// specialised turns): the header's nodes and edges and every edge's node word
+// src | dst << 16, in the bubble's edge order.  A bubble's structure id is 1 +
+// its index in its class's list, 0 when it is not listed; layout_slots writes
+// it into bits 8..15 of the table header (nodes <= 8 fits the low byte).  The
+// lists come from the corpora's histograms (profiles/bubble_shapes/histogram.txt):
+// the structures that carry c3's class-B waves, and the diamond.
+struct BubbleShape {
+    int nodes, edges;
+    int sd[kBubbleRegEdges];
+};
+constexpr int bubble_sd(int src, int dst) { return src | dst << 16; }
+#define WFSA_SD(s, d) bubble_sd(s, d)
+constexpr BubbleShape kBubbleShapesA[] = {
+    {4, 4, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 3)}},   // the diamond: all of c3's class A
+};
+// c3's thirteen class-B structures, by bubble count (13078, 4900, 1690, 877,
+// 699, 681, 129, 84, 57, 24, 23, 12, 6 of 22260): with any of them left to
+// the generic turn, the waves holding it run that turn beside the
+// specialised ones and end later than before
+constexpr BubbleShape kBubbleShapesB[] = {
+    {6, 6, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(3, 5), WFSA_SD(4, 5)}},
+    {5, 6, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(0, 3), WFSA_SD(1, 4), WFSA_SD(2, 4), WFSA_SD(3, 4)}},
+    {8, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(3, 5), WFSA_SD(4, 6), WFSA_SD(5, 7), WFSA_SD(6, 7)}},
+    {7, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(1, 5), WFSA_SD(3, 6), WFSA_SD(4, 6), WFSA_SD(5, 6)}},
+    {6, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(0, 3), WFSA_SD(0, 4), WFSA_SD(1, 5), WFSA_SD(2, 5), WFSA_SD(3, 5), WFSA_SD(4, 5)}},
+    {7, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(2, 5), WFSA_SD(3, 6), WFSA_SD(4, 6), WFSA_SD(5, 6)}},
+    {6, 7, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 3), WFSA_SD(2, 4), WFSA_SD(3, 5), WFSA_SD(4, 5)}},
+    {6, 7, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(2, 3), WFSA_SD(3, 5), WFSA_SD(4, 5)}},
+    {8, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(2, 3), WFSA_SD(1, 4), WFSA_SD(3, 5), WFSA_SD(4, 6), WFSA_SD(5, 7), WFSA_SD(6, 7)}},
+    {8, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(3, 5), WFSA_SD(4, 6), WFSA_SD(6, 7), WFSA_SD(5, 7)}},
+    {8, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(2, 3), WFSA_SD(1, 4), WFSA_SD(3, 5), WFSA_SD(4, 6), WFSA_SD(6, 7), WFSA_SD(5, 7)}},
+    {8, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(4, 5), WFSA_SD(3, 6), WFSA_SD(6, 7), WFSA_SD(5, 7)}},
+    {8, 8, {WFSA_SD(0, 1), WFSA_SD(0, 2), WFSA_SD(1, 3), WFSA_SD(2, 4), WFSA_SD(4, 5), WFSA_SD(3, 6), WFSA_SD(5, 7), WFSA_SD(6, 7)}},
+};
+#undef WFSA_SD
+constexpr int kBubbleShapesNA = int(sizeof(kBubbleShapesA) / sizeof(BubbleShape));
+constexpr int kBubbleShapesNB = int(sizeof(kBubbleShapesB) / sizeof(BubbleShape));
+constexpr int kBubbleShapeShift = 8, kBubbleShapeMask = 0xff << kBubbleShapeShift;
+// the id of the structure (header hdr, node words sd[stride * e]) in the class
+// of RE edges per bubble
+inline int bubble_shape_id(int RE, int hdr, const int32_t* sd, int stride) {
+    const BubbleShape* list = RE == 4 ? kBubbleShapesA : kBubbleShapesB;
+    const int n = RE == 4 ? kBubbleShapesNA : kBubbleShapesNB;
+    for (int i = 0; i < n; ++i) {
+        bool same = hdr == (list[i].nodes | list[i].edges << 16);
+        for (int e = 0; same && e < list[i].edges; ++e) same = sd[size_t(stride) * size_t(e)] == list[i].sd[e];
+        if (same) return i + 1;
+    }
+    return 0;
+}
 struct BubbleArgs {
     ModelView m;
     const int4* sm4_tbl;     // class A table (most bubbles: diamonds)

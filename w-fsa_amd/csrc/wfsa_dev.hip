@@ -28,6 +28,8 @@
 #include <cstring>
 #include <memory>
 #include <limits>
+#include <map>
+#include <set>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -410,6 +412,8 @@ struct wfsa_dev {
     bool qw_last_self = true;        // a Run's last launch finishes its own step (WFSA_QN_LAST_SELF=0: off)
     bool use_ll_dot = true;          // evaluations without log q skip the stream pass: the trivial words'
                                      // log-likelihood as a dot product (step_dot_kernel; WFSA_LL_DOT=0: fbs_kernel)
+    bool use_bubble_shapes = true;   // the small-bubble tables carry structure ids (wfsa::kBubbleShapesA / B;
+                                     // WFSA_BUBBLE_SHAPES=0: every id 0, the generic sweeps)
     uint64_t qw_seq = 0;             // in-kernel QN launches enqueued (their parity)
     wfsa::QnWave qw_next{};          // picked up by the next stream kernel launch (qw_next.on)
     DevBuf<unsigned long long> fbs_trace;   // timing experiments (WFSA_FBS_TRACE): per-wave stamps of the last launch
@@ -1252,16 +1256,33 @@ int layout_slots(wfsa_dev* ctx, const std::vector<int32_t>& pos_of) {
                 const int32_t f = phys(pos, fill[size_t(pos)]++) | (int32_t(k) << 28);
                 for (int64_t q = b; q < b + (int64_t(1) << k); ++q) sfield[size_t(q) * 8 + size_t(e)] = f;
             }
-        // class tables: RE edges, quads = 1 + RE/2 + RE/4
+        // class tables: RE edges, quads = 1 + RE/2 + RE/4; the header's bits
+        // 8..15 carry the bubble's structure id (wfsa::bubble_shape_id), by
+        // which a wave dispatches to the sweeps compiled for the structure
+        ctx->stats.shaped_bubbles = ctx->stats.mixed_shape_waves = 0;
+        ctx->stats.small_bubbles_a = n4;
+        ctx->stats.small_bubbles_b = nsm - n4;
         auto build_table = [&](const std::vector<int32_t>& list, int RE, std::vector<int32_t>& tbl, int64_t b_first) {
             const int Q = 1 + RE / 2 + RE / 4;
             const size_t n = list.size();
             tbl.assign(size_t(Q) * 4 * std::max<size_t>(n, 1), 0);
             auto quad = [&](int k, size_t b) { return &tbl[(size_t(k) * n + b) * 4]; };
+            int wave_id = 0;
+            bool mixed = false;
             for (size_t b = 0; b < n; ++b) {
                 const int32_t o = list[b];
                 const int edges = bb[size_t(o)] >> 16;
                 for (int w = 0; w < 4; ++w) quad(0, b)[w] = bb[size_t(o) + size_t(w)];
+                const int id = ctx->use_bubble_shapes ? wfsa::bubble_shape_id(RE, bb[size_t(o)], &bb[size_t(o) + 5], 2) : 0;
+                quad(0, b)[0] |= id << wfsa::kBubbleShapeShift;
+                ctx->stats.shaped_bubbles += id != 0;
+                if (b % size_t(kWave) == 0) {   // (a wave: 64 consecutive entries from the class's first)
+                    wave_id = id;
+                    mixed = false;
+                } else if (id != wave_id && !mixed) {
+                    mixed = true;
+                    ++ctx->stats.mixed_shape_waves;
+                }
                 for (int e = 0; e < RE; ++e) {
                     int32_t code = np, sd = 0, sl = -1;   // padding edges: the zero-slot code
                     if (e < edges) {
@@ -1890,6 +1911,48 @@ int prepare(wfsa_dev* ctx, int level) {
         };
         std::stable_sort(small4.begin(), small4.end(), shape_less);
         std::stable_sort(small.begin(), small.end(), shape_less);
+        if (std::getenv("WFSA_VERBOSE")) {   // the classes' structures (header and node words) and their mix per wave
+            int cls = 0;
+            for (const auto* list : {&small4, &small}) {
+                auto key_of = [&](int32_t o) {
+                    std::vector<int32_t> k(1, h_bubbuf[size_t(o)]);
+                    for (int e = 0; e < (h_bubbuf[size_t(o)] >> 16); ++e) k.push_back(h_bubbuf[size_t(o) + 5 + 2 * size_t(e)]);
+                    return k;
+                };
+                std::map<std::vector<int32_t>, int64_t> count;
+                int64_t waves[3] = {0, 0, 0};
+                for (size_t b0 = 0; b0 < list->size(); b0 += size_t(kWave)) {
+                    std::set<std::vector<int32_t>> in_wave;
+                    for (size_t b = b0; b < std::min(list->size(), b0 + size_t(kWave)); ++b) {
+                        const std::vector<int32_t> k = key_of((*list)[b]);
+                        ++count[k];
+                        in_wave.insert(k);
+                    }
+                    ++waves[std::min<size_t>(in_wave.size(), 3) - 1];
+                }
+                std::vector<std::pair<int64_t, std::vector<int32_t>>> by_count;
+                for (const auto& kv : count) by_count.emplace_back(kv.second, kv.first);
+                std::sort(by_count.begin(), by_count.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
+                std::fprintf(stderr, "[bubble-shapes] class %c: %zu bubbles, %zu structures; waves holding 1 / 2 / 3+ structures: "
+                             "%lld / %lld / %lld\n", cls ? 'B' : 'A', list->size(), by_count.size(), (long long)waves[0],
+                             (long long)waves[1], (long long)waves[2]);
+                for (size_t i = 0; i < std::min<size_t>(by_count.size(), 24); ++i) {
+                    const std::vector<int32_t>& k = by_count[i].second;
+                    std::fprintf(stderr, "[bubble-shapes]   %8lld x id %d: nodes %d edges %d:", (long long)by_count[i].first,
+                                 wfsa::bubble_shape_id(cls ? wfsa::kBubbleRegEdges : 4, k[0], k.data() + 1, 1), k[0] & 0xffff,
+                                 k[0] >> 16);
+                    for (size_t e = 1; e < k.size(); ++e) std::fprintf(stderr, " %d>%d", k[e] & 0xffff, k[e] >> 16);
+                    std::fprintf(stderr, "\n");
+                }
+                if (by_count.size() > 24) {
+                    int64_t rest = 0;
+                    for (size_t i = 24; i < by_count.size(); ++i) rest += by_count[i].first;
+                    std::fprintf(stderr, "[bubble-shapes]   and %zu more structures (%lld bubbles)\n", by_count.size() - 24,
+                                 (long long)rest);
+                }
+                ++cls;
+            }
+        }
         {   // list position of every bubble (the fused rmin values are stored there)
             std::unordered_map<int32_t, int32_t> idx_of;
             idx_of.reserve(h_off.size());
@@ -2810,7 +2873,17 @@ bool qw_usable(wfsa_dev* ctx) {
     // batches within the areas' flags)
     const bool comm_ok = !ctx->comm || (std::strcmp(ctx->comm->peer_state(), "on") == 0 &&
                                         ctx->qw_nbatch <= wfsa::kPeerMaxQnBatches);
-    return ctx->use_qw && (ctx->qw_cover || ctx->qw_force) && ctx->qw_ok && ctx->qw_waves > 0 && ctx->qn_fused &&
+    // The cover rule holds where a stream pass or the folded rmin column
+    // runs beside the bubbles.  A step_dot_kernel step without the column
+    // has nothing to cover its QN waves' wait for the last bubble arrival:
+    // the two kernels are faster at every measured size (200k / 500k / 1M
+    // strings: 16.4-16.8 / 16.5-17.6 / 18.2-18.7 against 17.7-18.2 /
+    // 20.6-20.8 / 21.5-21.9 us per step; with the column the one launch
+    // still wins at 1M, 23.5 against 26.2;
+    // profiles/bubble_shapes/cover_timings.txt).  Across ranks the rule
+    // stays: no measurement to change it on.
+    const bool cover = ctx->qw_cover && !(ll_dot(ctx, false, false) && !ctx->comm && !ctx->qn_rmin);
+    return ctx->use_qw && (cover || ctx->qw_force) && ctx->qw_ok && ctx->qw_waves > 0 && ctx->qn_fused &&
            comm_ok && !ctx->dense &&
            !ctx->mpath && rmin_ok && ctx->n_groups > 0 && ctx->delta_on && ctx->i_tables >= 1 &&
            ctx->fixed_t_on && ctx->qn_k > 0 &&
@@ -3142,6 +3215,7 @@ int wfsa_dev_create(int device, wfsa_dev** out) {
     }
     if (const char* e = std::getenv("WFSA_QN_LAST_SELF")) ctx->qw_last_self = e[0] != '0';
     if (const char* e = std::getenv("WFSA_LL_DOT")) ctx->use_ll_dot = e[0] != '0';
+    if (const char* e = std::getenv("WFSA_BUBBLE_SHAPES")) ctx->use_bubble_shapes = e[0] != '0';
 
     HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&ctx->ev0));
@@ -3971,7 +4045,9 @@ static int qn_run_impl(wfsa_dev* ctx, double eta, double tol, int32_t max_steps,
                 for (int k = 0; k < 4; ++k)
                     if (pts[k] && pts[k + 1]) ph[k].push_back(double(pts[k + 1] - pts[k]) / 100.0);
             }
-            const char* pn[4] = {"quads", "gathers", "forward", "backward"};
+            // (stamp 10: after both sweeps in the kernels with the per-structure sweeps, small_bubble's
+            // phases 1 and 2; after the forward sweep alone in the others, whose backward sweep sums and stores)
+            const char* pn[4] = {"quads", "gathers", "forward|sweeps", "backward|sums+stores"};
             std::fprintf(stderr, "[fbs-trace] class %c small-bubble phases (p50 / p90 / max us):", cls ? 'B' : 'A');
             for (int k = 0; k < 4; ++k) {
                 if (ph[k].empty()) continue;

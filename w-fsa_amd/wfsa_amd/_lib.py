@@ -53,6 +53,7 @@ class DevStats(C.Structure):
         ("stream_delta", i32), ("bubbles_fused", i32), ("grad_tables", i32), ("wave_lgrad", i32),
         ("ll_dot_launches", i64), ("best_path_ms", dbl), ("kbest_path_ms", dbl),
         ("sample_path_ms", dbl), ("posterior_count_ms", dbl), ("byte_marginal_ms", dbl),
+        ("shaped_bubbles", i64), ("mixed_shape_waves", i64), ("small_bubbles_a", i64), ("small_bubbles_b", i64),
     ]
 
 
