@@ -135,6 +135,9 @@ typedef struct {
     int64_t mixed_shape_waves; /* small-bubble waves whose lanes carry more than one structure id (several sweep turns) */
     int64_t small_bubbles_a;   /* small bubbles of class A (<= 4 nodes and edges), one lane each */
     int64_t small_bubbles_b;   /* small bubbles of class B (<= 8 nodes and edges); n_bubbles counts the big ones too */
+    int64_t big_bubbles;       /* bubbles of neither class (more nodes or edges, or a multi-parameter edge), one wave each */
+    int32_t max_bubble_nodes;  /* nodes of the largest compiled bubble (at most 32; 0: no bubble) */
+    int32_t max_bubble_edges;  /* edges of the compiled bubble with the most edges (at most 255; 0: no bubble) */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */

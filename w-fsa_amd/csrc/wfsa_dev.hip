@@ -324,6 +324,7 @@ struct wfsa_dev {
     DevBuf<int4> rm_amb;         // the ambiguous strings (path count > 1) with their bubble runs
     std::vector<int32_t> h_bfirst, h_nbub;   // per string: first bubble ordinal, bubbles (compiled strings)
     int max_bub_nodes = 1;                   // largest compiled bubble (nodes)
+    int max_bub_edges = 0;                   // most edges of a compiled bubble (stats)
     int64_t rm_n_amb = 0;
     // the rmin column folded into the in-kernel QN step (fb_kernels.hpp RminFold)
     std::vector<int32_t> h_bpos;    // list position of each bubble (layout)
@@ -1890,10 +1891,12 @@ int prepare(wfsa_dev* ctx, int level) {
         auto edge_code_at = [&](int32_t o, int e) { return h_bubbuf[size_t(o) + 4 + 2 * size_t(e)]; };
         std::vector<int32_t> small4, small, big;
         ctx->max_bub_nodes = 1;
+        ctx->max_bub_edges = 0;
         for (int32_t o : h_off) {
             const int hdr = h_bubbuf[size_t(o)];
             const int nodes = hdr & 0xffff, edges = hdr >> 16;
             ctx->max_bub_nodes = std::max(ctx->max_bub_nodes, nodes);
+            ctx->max_bub_edges = std::max(ctx->max_bub_edges, edges);
             bool sm = edges <= wfsa::kBubbleRegEdges && nodes <= wfsa::kBubbleRegNodes;
             for (int e = 0; sm && e < edges; ++e) sm = edge_code_at(o, e) >= 0;
             (!sm ? big : (edges <= 4 && nodes <= 4 ? small4 : small)).push_back(o);
@@ -2193,6 +2196,9 @@ int prepare(wfsa_dev* ctx, int level) {
     ctx->stats.stream_words = words;
     ctx->stats.stream_bytes = ctx->delta_on ? ctx->d_stream_bytes : chunks * 16;   // what the per-iteration pass reads
     ctx->stats.n_bubbles = nbub;
+    ctx->stats.big_bubbles = ctx->n_big;
+    ctx->stats.max_bubble_nodes = nbub > 0 ? ctx->max_bub_nodes : 0;
+    ctx->stats.max_bubble_edges = nbub > 0 ? ctx->max_bub_edges : 0;
     ctx->stats.bubble_words = bwords;
     ctx->stats.tier1_strings = n_tier1;
     ctx->stats.waves_per_block = ctx->cfg[0].waves_per_block;

@@ -54,6 +54,7 @@ class DevStats(C.Structure):
         ("ll_dot_launches", i64), ("best_path_ms", dbl), ("kbest_path_ms", dbl),
         ("sample_path_ms", dbl), ("posterior_count_ms", dbl), ("byte_marginal_ms", dbl),
         ("shaped_bubbles", i64), ("mixed_shape_waves", i64), ("small_bubbles_a", i64), ("small_bubbles_b", i64),
+        ("big_bubbles", i64), ("max_bubble_nodes", i32), ("max_bubble_edges", i32),
     ]
 
 
