@@ -2153,6 +2153,15 @@ __device__ __forceinline__ double group_sum(double v, int k, int kmax) {
 #ifndef WFSA_BIG_PRIO
 #define WFSA_BIG_PRIO 3
 #endif
+// The class-B small-bubble waves' priority in step_dot_kernel: the big
+// bubbles', above class A's 2.  Their chain (quads, gathers, the longest
+// sweeps, sums and stores) is the launch's critical path, and their chunks
+// sit on waves 3 and 4 of a block, which otherwise lose the issue arbitration
+// to the older class-A waves of their SIMD (c3 18.0 vs 18.6 us per step, the
+// step kernel 10.6 vs 11.3 us; profiles/step_entry/ab_default.txt)
+#ifndef WFSA_SMALL_B_PRIO
+#define WFSA_SMALL_B_PRIO 3
+#endif
 // (tr: timing experiments only, stamps 8..11 of the wave's trace row)
 #define WFSA_BSTAMP(k)                                                   \
     if (tr) {                                                            \
@@ -3563,8 +3572,9 @@ __global__ __launch_bounds__(1024) void step_dot_kernel(CompiledArgs a) {
         blk_in = 0u;
         if (QN) q_arrived = 0u;
     }
-    // the wave's share of the trivial words' log-likelihood: its loads in
-    // flight from entry, waited for with the bubbles' first loads
+    // the wave's share of the trivial words' log-likelihood (its two loads
+    // are waited for here, inside its loop: one round trip before the barrier;
+    // issuing them earlier did not shorten the step, DESIGN section 3a, Loads at entry)
     double ll_acc = ll_trivial_share(a.ll_coef, a.w, a.n_params, gw * kWave + lane, nw * kWave);
     __syncthreads();   // (the counters above; every wave is at entry: nothing waits here)
     WFSA_STAMP(1)
@@ -3593,6 +3603,8 @@ __global__ __launch_bounds__(1024) void step_dot_kernel(CompiledArgs a) {
 #endif
             __builtin_amdgcn_s_setprio(2);
             const BubbleArgs bub = WFSA_LATE_ARG(bub);
+            // (a wave holds one class: its lanes' entries are all below n_small4 or all from it on)
+            if (WFSA_SMALL_B_PRIO != 2 && __ballot(b >= bub.n_small4) != 0ull) __builtin_amdgcn_s_setprio(WFSA_SMALL_B_PRIO);
             const RminFold rf = WFSA_LATE_ARG(rf);
             const RminFold* rfp = RF ? &rf : nullptr;
             RminLane* rlp = RF ? &rm_lane : nullptr;
