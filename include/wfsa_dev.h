@@ -138,6 +138,7 @@ typedef struct {
     int64_t big_bubbles;       /* bubbles of neither class (more nodes or edges, or a multi-parameter edge), one wave each */
     int32_t max_bubble_nodes;  /* nodes of the largest compiled bubble (at most 32; 0: no bubble) */
     int32_t max_bubble_edges;  /* edges of the compiled bubble with the most edges (at most 255; 0: no bubble) */
+    double generate_ms;        /* last wfsa_dev_generate call: device time of its kernels */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -454,6 +455,70 @@ int wfsa_dev_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t decode,
 int wfsa_dev_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow /* [total_symbols + 1] */, int32_t* midx /* [n_entries] */,
                                 double* mval /* [n_entries] */);
 int wfsa_dev_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow /* [n_strings + 1] */, int32_t* pidx /* [n_path_entries] */);
+
+/* Unconditional generation: n independent strings drawn from the automaton
+ * itself at w_full, each with its path and weights.  The call needs a loaded
+ * model only, no corpus, and no trellis: it walks the flattened state graph of
+ * wfsa_model_desc (generate.hip), so it serves a model on the dense path too.
+ *
+ * The walk.  Sample i (0 <= i < n) starts at U = start with step m = 0.  Each
+ * step makes two choices:
+ *   - draw 2m chooses one of U's transitions tr_ptr[U] .. tr_ptr[U + 1], to V;
+ *   - if V is `end`, the sample is complete (status 0);
+ *   - otherwise draw 2m + 1 chooses one of V's emissions em_ptr[V] ..
+ *     em_ptr[V + 1];
+ *   - if its bytes would take the string past max_len, the sample is truncated
+ *     (status 1) and that emission is not recorded (the transition into V,
+ *     chosen before it, is);
+ *   - else the bytes are appended, U = V and m += 1.
+ * A choice.  The candidates have masses a_k = exp(w_full[param_k]); the member
+ * of a single-member group (param = -1) has a_k = 1.0.  The running sums are
+ * formed left to right in the model's order (one add per candidate, no fused
+ * multiply-add), T is the last of them.  The choice takes the first k whose
+ * running sum exceeds u * T; if rounding leaves none, the last candidate of
+ * positive mass -- sample_paths' rule word for word.  No candidates, or T == 0,
+ * leaves the sample dead (status 2): the model loses that mass.  A dead sample
+ * keeps what was recorded before the choice that failed.  (The device finds k
+ * by bisection in the running sums, which do not decrease and which a
+ * candidate of mass 0 leaves unchanged: the same k.)
+ * The draws.  u of draw d of sample i is sample_paths' generator with key
+ * (lo32(seed), hi32(seed)) and counter (lo32(i), hi32(i), 0xFFFFFFFF, d): the
+ * sample word 0xFFFFFFFF is one sample_paths (t < 64) never uses.
+ *
+ *   *total_bytes     = bytes of all samples (NULL allowed);
+ *   *n_entries       = total length of their parameter lists (NULL allowed);
+ *   status_counts[3] = samples complete, truncated, dead (NULL allowed).
+ * generate_get copies the samples out (every pointer may be NULL): sample i's
+ * bytes are sym[off[i] .. off[i + 1]); pidx[prow[i] .. prow[i + 1]) are the Fsa
+ * parameter ids in path order, a transition before the emission it leads to,
+ * repeats kept, single-member groups carrying no id (best_paths_get's
+ * convention); logw[i] is the left-to-right sum of the chosen parameters'
+ * weights, the decoders' path weight; logp[i] is the left-to-right sum of
+ * w_k - log T over the choices (0 - log 1 for a single-member group), the log
+ * probability of the walk itself, equal to logw when every group sums to 1;
+ * status[i] as above.  A truncated or dead sample keeps the bytes, path, logw
+ * and logp of the choices recorded before it stopped.
+ *
+ * Reproducibility.  The same weights, max_len and seed give the same bytes on
+ * every call; sample i depends neither on n nor on which wave or lane walked
+ * it, so the first j samples of an n result are the j result byte for byte.
+ *
+ * Valid until the next load or generate call.  It invalidates none of the
+ * other results (best_paths, kbest_paths, sample_paths, posterior_counts,
+ * byte_marginals) and none of them invalidates it.  Local to the rank (no
+ * collective), and leaves the learning path untouched, as the decoders do.
+ * WFSA_ERR_ARG before a model is loaded, in matrix-file mode, while an
+ * evaluation is in flight, for n < 1, max_len < 0 or
+ * 2 * n_states * (max_len + 1) >= 2^32 (the draw index is a 32-bit counter
+ * word; a loaded model has no epsilon cycle, so no walk takes more than
+ * n_states * (max_len + 1) steps), for a w_full entry that is NaN or +inf
+ * (before any walk), and from _get without a result since the last load;
+ * WFSA_ERR_CAPACITY when the bytes or the path entries exceed 4 GiB, and for
+ * n >= 2^31. */
+int wfsa_dev_generate(wfsa_dev* ctx, const double* w_full, int64_t n, int32_t max_len, uint64_t seed,
+                      int64_t* total_bytes, int64_t* n_entries, int64_t status_counts[3]);
+int wfsa_dev_generate_get(wfsa_dev* ctx, uint8_t* sym, int64_t* off /* [n + 1] */, double* logw /* [n] */, double* logp /* [n] */,
+                          int8_t* status /* [n] */, int64_t* prow /* [n + 1] */, int32_t* pidx /* [n_entries] */);
 
 /* Where each loaded string runs (after compilation): tier[s] = -1 compiled
  * stream (trivial words + bubbles), 0 / 1 LDS-slab traversal, 2 wide

@@ -27,6 +27,10 @@ void wfsa_fsa_free(wfsa_fsa* fsa);
 int wfsa_fsa_desc(wfsa_fsa* fsa, wfsa_model_desc* out);
 /* counts: states, transitions, emissions, parameters, constraints, free params */
 int wfsa_fsa_counts(wfsa_fsa* fsa, int64_t out[6]);
+/* the automaton's weights as read (log values), out[parameters], in Fsa
+ * parameter-index order: the w_full of an automaton nobody has trained (what
+ * wfsa_dev_generate takes without a corpus) */
+int wfsa_fsa_weights(wfsa_fsa* fsa, double* out);
 /* state id (wfsa_model_desc numbering, 0 .. states - 1) -> its name (valid while fsa lives) */
 int wfsa_fsa_state_name(wfsa_fsa* fsa, int32_t state, const char** name);
 /* Fsa parameter j -> owning state name, kind (0 emission / 1 transition), label */
@@ -140,6 +144,18 @@ int wfsa_learner_sample_paths(wfsa_learner* l, int32_t n, uint64_t seed, double*
                               int64_t* n_paths, int64_t* n_entries);
 int wfsa_learner_sample_paths_get(wfsa_learner* l, int64_t* srow /* [n_local_strings + 1] */, double* logw /* [n_paths] */,
                                   int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
+/* Unconditional generation at the current x (wfsa_dev_generate with w_full
+ * from GetWeight; after a device-resident run, the state it left): n strings
+ * drawn from the automaton itself, at most max_len bytes each, reproducible
+ * from `seed` as wfsa_dev.h states.  *total_bytes, *n_entries and
+ * status_counts[3] (complete, truncated, dead) may be NULL.  generate_get
+ * copies the samples out in wfsa_dev_generate_get's layout (any pointer may be
+ * NULL).  Local to the rank: no collective. */
+int wfsa_learner_generate(wfsa_learner* l, int64_t n, int32_t max_len, uint64_t seed, int64_t* total_bytes, int64_t* n_entries,
+                          int64_t status_counts[3]);
+int wfsa_learner_generate_get(wfsa_learner* l, uint8_t* sym, int64_t* off /* [n + 1] */, double* logw /* [n] */,
+                              double* logp /* [n] */, int8_t* status /* [n] */, int64_t* prow /* [n + 1] */,
+                              int32_t* pidx /* [n_entries] */);
 /* Posterior expected counts at the current x (wfsa_dev_posterior_counts with
  * w_full from GetWeight): per local recognized string, in get_p's order, its
  * log q, the entropy of its path posterior (nats) and the sparse row of expected

@@ -172,6 +172,17 @@ void Fsa::Dump(FILE* out) const {
     }
 }
 
+std::vector<double> fsa_weights(const Fsa& fsa) {
+    std::vector<double> w(fsa.GetNumberOfParameters(), 0.0);
+    for (const auto& s : fsa.GetTransitionMtx()) {
+        for (const auto& e : s.second.emissions)
+            if (e.index >= 0) w[size_t(e.index)] = e.logprob;
+        for (const auto& t : s.second.transitions)
+            if (t.index >= 0) w[size_t(t.index)] = t.logprob;
+    }
+    return w;
+}
+
 FlatModel::FlatModel(const Fsa& fsa) {
     const auto& mtx = fsa.GetTransitionMtx();
     std::unordered_map<const void*, int32_t> id;

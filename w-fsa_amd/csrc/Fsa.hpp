@@ -75,6 +75,11 @@ private:
     std::vector<char> content;   // tokenized copy; state/emission names live here
 };
 
+// The automaton's weights as it holds them now (as read, or after a learner's
+// RewriteWeights), in parameter-index order: w_full for a device call that
+// has no learner (generation without a corpus).
+std::vector<double> fsa_weights(const Fsa& fsa);
+
 // The automaton flattened for wfsa_dev_load_model.  State ids follow the
 // Fsa's map iteration order; names are kept for reporting.
 struct FlatModel {

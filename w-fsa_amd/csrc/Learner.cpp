@@ -623,6 +623,23 @@ void Learner::SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t
     ThrowOnDevError(rc, "wfsa_dev_sample_paths_get");
 }
 
+void Learner::Generate(int64_t n, int32_t max_len, uint64_t seed, int64_t* total_bytes, int64_t* n_entries, int64_t* status_counts) {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
+    const double none = 0.0;
+    get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
+    const int rc = wfsa_dev_generate(dev, w_full.data(), n, max_len, seed, total_bytes, n_entries, status_counts);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_generate: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_generate");
+}
+
+void Learner::GenerateGet(uint8_t* sym, int64_t* off, double* logw, double* logp, int8_t* status, int64_t* prow, int32_t* pidx) const {
+    if (!dev) throw LearnerUsageError("BuildFrom has not run");
+    const int rc = wfsa_dev_generate_get(dev, sym, off, logw, logp, status, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_generate_get: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_generate_get");
+}
+
 void Learner::PosteriorCounts(double* logq, double* entropy, int64_t* n_entries) {
     if (!dev) throw LearnerUsageError("BuildFrom has not run");
     if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");

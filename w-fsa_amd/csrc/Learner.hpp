@@ -160,6 +160,13 @@ public:
     // string's n paths in sample order
     void SamplePaths(int32_t n, uint64_t seed, double* logq, int64_t* n_paths, int64_t* n_entries);
     void SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const;
+    // Unconditional generation at the current x (wfsa_dev_generate with
+    // GetWeight's w_full): n strings drawn from the automaton itself, at most
+    // max_len bytes each; total_bytes, n_entries and status_counts[3]
+    // (complete, truncated, dead) nullable.  GenerateGet copies the samples
+    // out in wfsa_dev_generate_get's layout
+    void Generate(int64_t n, int32_t max_len, uint64_t seed, int64_t* total_bytes, int64_t* n_entries, int64_t* status_counts);
+    void GenerateGet(uint8_t* sym, int64_t* off, double* logw, double* logp, int8_t* status, int64_t* prow, int32_t* pidx) const;
     // Posterior expected counts at the current x (wfsa_dev_posterior_counts
     // with GetWeight's w_full): per local recognized string its log q, the
     // entropy of its path posterior and the sparse row of expected parameter

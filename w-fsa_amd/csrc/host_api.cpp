@@ -154,6 +154,14 @@ int wfsa_fsa_counts(wfsa_fsa* f, int64_t out[6]) {
     return WFSA_OK;
 }
 
+int wfsa_fsa_weights(wfsa_fsa* f, double* out) {
+    if (!f || !out) return null_arg("fsa/out");
+    return guarded([&] {
+        const std::vector<double> w = fsa_weights(f->fsa);
+        if (!w.empty()) std::memcpy(out, w.data(), w.size() * sizeof(double));
+    });
+}
+
 int wfsa_fsa_state_name(wfsa_fsa* f, int32_t state, const char** name) {
     if (!f || !name) return null_arg("fsa/name");
     return guarded([&] {
@@ -451,6 +459,18 @@ int wfsa_learner_sample_paths(wfsa_learner* l, int32_t n, uint64_t seed, double*
 int wfsa_learner_sample_paths_get(wfsa_learner* l, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
     if (!l) return null_arg("learner");
     return guarded([&] { l->base->SamplePathsGet(srow, logw, prow, pidx); });
+}
+
+int wfsa_learner_generate(wfsa_learner* l, int64_t n, int32_t max_len, uint64_t seed, int64_t* total_bytes, int64_t* n_entries,
+                          int64_t status_counts[3]) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->host(false).Generate(n, max_len, seed, total_bytes, n_entries, status_counts); });   // (no collective: nothing to abort)
+}
+
+int wfsa_learner_generate_get(wfsa_learner* l, uint8_t* sym, int64_t* off, double* logw, double* logp, int8_t* status, int64_t* prow,
+                              int32_t* pidx) {
+    if (!l) return null_arg("learner");
+    return guarded([&] { l->base->GenerateGet(sym, off, logw, logp, status, prow, pidx); });
 }
 
 int wfsa_learner_posterior_counts(wfsa_learner* l, double* logq, double* entropy, int64_t* n_entries) {

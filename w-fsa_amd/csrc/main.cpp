@@ -5,6 +5,7 @@
 //   wfsa -a A.wfsa -c C.corpus [-opt Hessian|QuasiNewton] [-e epochs] [-l eta]
 //        [-tol t] [-i flags] [-n] [-eval] [-s] [-o out.wfsa] [-x] [-p] [-bp best.tsv] [-kbp K kbest.tsv]
 //        [-sp N samples.tsv [--sample-seed S]] [-pc counts.tsv] [-d device]
+//   wfsa -a A.wfsa -gen N out.corpus [--gen-max-len L] [--sample-seed S]   (no corpus: the weights as read)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +13,7 @@
 #include <iostream>
 #include <memory>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "Corpus.hpp"
@@ -50,7 +52,13 @@ void usage() {
                  "                         string, rank (1 = best), log weight, weight / q, Fsa parameter indices in path order\n"
                  "  -sp, --sample-paths N FILE  likewise N (1 .. 64) paths drawn at random from its posterior, one line each:\n"
                  "                         string, sample index (0 first), log weight, weight / q, Fsa parameter indices in path order\n"
-                 "  --sample-seed S        seed of -sp's random numbers (0); the same seed gives the same file\n"
+                 "  --sample-seed S        seed of -sp's and -gen's random numbers (0); the same seed gives the same file\n"
+                 "  -gen, --generate N FILE  draw N strings from the automaton itself and write the distinct complete ones\n"
+                 "                         with their counts as a corpus (separator TAB).  Without -c nothing is learned\n"
+                 "                         and the weights are those read from the automaton; with -c, the final weights.\n"
+                 "                         Truncated and dead samples, the empty string and strings holding TAB, newline\n"
+                 "                         or NUL are left out and counted on stderr\n"
+                 "  --gen-max-len L        longest string -gen draws, in bytes (255); a longer one is truncated\n"
                  "  -pc, --posterior-counts FILE  likewise its posterior expected counts, one line per recognized string:\n"
                  "                         string, log q, entropy of its path posterior (nats), then id:count per Fsa parameter\n"
                  "                         used in expectation, ascending ids (tab separated)\n"
@@ -63,11 +71,43 @@ void usage() {
                  "  -d, --device N         GPU to use (0)\n";
 }
 
+// -gen: the distinct complete samples with their counts, in first-appearance
+// order, as a corpus file with separator TAB.  What the format cannot hold --
+// the empty string, a string with TAB, newline or NUL -- is left out and
+// counted on stderr, as are the truncated and the dead samples.
+void write_generated(const std::string& file, int64_t n, const std::vector<uint8_t>& sym, const std::vector<int64_t>& off,
+                     const std::vector<int8_t>& status, const int64_t status_counts[3]) {
+    std::unordered_map<std::string, size_t> index;
+    std::vector<std::pair<std::string, int64_t>> rows;
+    int64_t unwritable = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (status[size_t(i)] != 0) continue;
+        const std::string str(reinterpret_cast<const char*>(sym.data()) + off[size_t(i)], size_t(off[size_t(i) + 1] - off[size_t(i)]));
+        if (str.empty() || str.find_first_of(std::string("\t\n\0", 3)) != std::string::npos) {
+            ++unwritable;
+            continue;
+        }
+        const auto it = index.emplace(str, rows.size());
+        if (it.second) rows.emplace_back(str, 0);
+        ++rows[it.first->second].second;
+    }
+    FILE* gf = std::fopen(file.c_str(), "w");
+    if (!gf) throw MyError("Unable to open \"", file, "\" for writing!");
+    std::fputs("\t\n", gf);
+    for (const auto& r : rows) std::fprintf(gf, "%s\t%lld\n", r.first.c_str(), (long long)r.second);
+    std::fclose(gf);
+    std::cerr << "Generate:\n\tsamples: " << n << "\n\tcomplete: " << status_counts[0] << "\n\ttruncated: " << status_counts[1]
+              << "\n\tdead: " << status_counts[2] << "\n\tunwritable: " << unwritable << "\n\tdistinct written: " << rows.size()
+              << std::endl;
+}
+
 }  // namespace
 
 int main(int argc, const char* argv[]) {
     std::string automaton, corpus_file, output, optimizer = "Hessian", matrices, best_paths, kbest_paths, sample_paths, posterior_counts, byte_marginals,
-        mea_decode;
+        mea_decode, generate;
+    long long n_generate = 0;
+    int gen_max_len = 255;
     int epochs = 20, initflags = 0, device = 0, kbest = 0, n_samples = 0;
     unsigned long long sample_seed = 0;
     double eta = 1.0, tol = 1e-6;
@@ -106,6 +146,11 @@ int main(int argc, const char* argv[]) {
         else if (a == "-pc" || a == "--posterior-counts") posterior_counts = next();
         else if (a == "-bm" || a == "--byte-marginals") byte_marginals = next();
         else if (a == "-md" || a == "--mea-decode") mea_decode = next();
+        else if (a == "-gen" || a == "--generate") {
+            n_generate = std::atoll(next());
+            generate = next();
+        }
+        else if (a == "--gen-max-len") gen_max_len = std::atoi(next());
         else if (a == "--sample-seed") sample_seed = std::strtoull(next(), nullptr, 10);
         else if (a == "-n" || a == "--normalize") normalize = true;
         else if (a == "-eval" || a == "--eval" || a == "--evaluate") evaluate = true;
@@ -128,6 +173,38 @@ int main(int argc, const char* argv[]) {
         return 1;
     }
     try {
+        if (!generate.empty() && corpus_file.empty() && matrices.empty()) {
+            // generation alone: no corpus, nothing to learn -- the model goes to the device as read
+            Fsa fsa;
+            if (FILE* f = std::fopen(automaton.c_str(), "rb")) {
+                fsa.Read(f);
+                std::fclose(f);
+            } else {
+                std::cerr << "\nUnable to open \"" << automaton << "\"!" << std::endl;
+                return 1;
+            }
+            const FlatModel flat(fsa);
+            const wfsa_model_desc desc = flat.desc();
+            const std::vector<double> w = fsa_weights(fsa);
+            wfsa_dev* dev = nullptr;
+            auto check = [&](int rc, const char* what) {
+                if (rc == WFSA_OK) return;
+                const std::string msg = wfsa_dev_last_error();
+                if (dev) wfsa_dev_destroy(dev);
+                throw MyError(what, ": ", msg);
+            };
+            check(wfsa_dev_create(device, &dev), "wfsa_dev_create");
+            check(wfsa_dev_load_model(dev, &desc), "wfsa_dev_load_model");
+            int64_t n_bytes = 0, n_entries = 0, counts[3] = {0, 0, 0};
+            check(wfsa_dev_generate(dev, w.data(), n_generate, gen_max_len, sample_seed, &n_bytes, &n_entries, counts), "wfsa_dev_generate");
+            std::vector<uint8_t> sym(size_t(n_bytes) + 1);
+            std::vector<int64_t> off(size_t(n_generate) + 1);
+            std::vector<int8_t> status(static_cast<size_t>(n_generate));
+            check(wfsa_dev_generate_get(dev, sym.data(), off.data(), nullptr, nullptr, status.data(), nullptr, nullptr), "wfsa_dev_generate_get");
+            wfsa_dev_destroy(dev);
+            write_generated(generate, n_generate, sym, off, status, counts);
+            return 0;
+        }
         std::unique_ptr<Learner> owner(optimizer == "Hessian" ? static_cast<Learner*>(new HessianLearner())
                                                                : static_cast<Learner*>(new QuasiNewtonLearner()));
         Learner& learner = *owner;
@@ -321,6 +398,16 @@ int main(int argc, const char* argv[]) {
                     std::fputc('\n', sf);
                 }
             std::fclose(sf);
+        }
+        if (!generate.empty()) {   // strings drawn from the automaton at the final x
+            if (!have_fsa) throw MyError("-gen needs an automaton (-a): matrix-file mode has none to walk");
+            int64_t n_bytes = 0, n_entries = 0, counts[3] = {0, 0, 0};
+            learner.Generate(n_generate, gen_max_len, sample_seed, &n_bytes, &n_entries, counts);
+            std::vector<uint8_t> sym(size_t(n_bytes) + 1);
+            std::vector<int64_t> off(size_t(n_generate) + 1);
+            std::vector<int8_t> status(static_cast<size_t>(n_generate));
+            learner.GenerateGet(sym.data(), off.data(), nullptr, nullptr, status.data(), nullptr, nullptr);
+            write_generated(generate, n_generate, sym, off, status, counts);
         }
         if (!posterior_counts.empty()) {   // the per-string E-step at the final x
             if (!have_fsa) throw MyError("-pc needs an automaton and a corpus (-a / -c): matrix-file mode has no trellis");

@@ -42,6 +42,7 @@
 #include "fb_kernels.hpp"
 #include "decode.hpp"
 #include "sample.hpp"
+#include "generate.hpp"
 #include "marginals.hpp"
 #include "posterior.hpp"
 #include "trellis_model.hpp"
@@ -489,6 +490,29 @@ struct wfsa_dev {
     std::vector<double> bm_mval;
     std::vector<int64_t> bp_prow;
     std::vector<int32_t> bp_pidx;
+    // Unconditional generation (wfsa_dev_generate; generate.hpp): the flattened
+    // state graph as wfsa_model_desc gives it (uploaded with the model, on the
+    // dense path too), the call's weights and running sums, the per-sample
+    // tables, the outputs -- and its last result for _get
+    bool gn_ready = false;              // the graph on the device belongs to the loaded model
+    bool gn_valid = false;              // the host holds a result for _get
+    int32_t gn_states = 0, gn_start = -1, gn_end = -1, gn_params = 0;
+    int64_t gn_n_em = 0, gn_n_tr = 0;
+    DevBuf<int32_t> gn_em_ptr, gn_em_len, gn_em_param, gn_tr_ptr, gn_tr_dst, gn_tr_param;
+    DevBuf<int64_t> gn_em_off;
+    DevBuf<uint8_t> gn_em_bytes;
+    DevBuf<double> gn_w, gn_cdf_tr, gn_cdf_em, gn_logw, gn_logp;
+    DevBuf<unsigned> gn_flag;
+    DevBuf<int32_t> gn_len, gn_plen, gn_pidx;
+    DevBuf<int8_t> gn_status;
+    DevBuf<int64_t> gn_bsum, gn_off, gn_prow;
+    DevBuf<uint8_t> gn_sym;
+    hipEvent_t gn_ev[4] = {};
+    std::vector<uint8_t> gn_h_sym;
+    std::vector<int64_t> gn_h_off, gn_h_prow;
+    std::vector<double> gn_h_logw, gn_h_logp;
+    std::vector<int8_t> gn_h_status;
+    std::vector<int32_t> gn_h_pidx;
     std::vector<int64_t> kb_srow, kb_prow;
     std::vector<double> kb_logw;
     std::vector<int32_t> kb_pidx;
@@ -3106,6 +3130,7 @@ void drop_graph(wfsa_dev* ctx) {
 // a load ends the decode results held for _get
 void invalidate_decodes(wfsa_dev* ctx) {
     ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = ctx->pc.valid = ctx->bm.valid = false;
+    ctx->gn_valid = false;
     ctx->bm_base_ok = false;   // (the state sums' addresses belong to one model and one corpus)
 }
 
@@ -3141,6 +3166,48 @@ int dense_load_corpus(wfsa_dev* ctx, const uint8_t* sym, const int64_t* off, con
     ctx->stats.dense_steps = ctx->dense->steps();
     ctx->stats.dense_np = ctx->dense->np();
     ctx->stats.dense_blas = ctx->dense->engine();
+    return WFSA_OK;
+}
+
+// The flattened state graph for wfsa_dev_generate (generate.hpp), as the
+// description gives it.  The walk trusts every index, so a description with an
+// index out of range is not uploaded (*ok = false; the model's own checks
+// reject it with their message, and generate refuses until a model loads).
+int upload_generate_graph(wfsa_dev* ctx, const wfsa_model_desc& m, bool* ok) {
+    *ok = false;
+    ctx->gn_ready = false;
+    const int32_t N = m.n_states;
+    if (N < 1 || m.start < 0 || m.start >= N || m.end >= N || m.n_params < 0) return WFSA_OK;
+    if (!m.em_ptr || !m.tr_ptr || m.em_ptr[0] != 0 || m.tr_ptr[0] != 0) return WFSA_OK;
+    for (int32_t u = 0; u < N; ++u)
+        if (m.em_ptr[u + 1] < m.em_ptr[u] || m.tr_ptr[u + 1] < m.tr_ptr[u]) return WFSA_OK;
+    const int64_t n_em = m.em_ptr[N], n_tr = m.tr_ptr[N];
+    if ((n_em > 0 && (!m.em_off || !m.em_len || !m.em_param)) || (n_tr > 0 && (!m.tr_dst || !m.tr_param))) return WFSA_OK;
+    int64_t n_bytes = 0;
+    for (int64_t k = 0; k < n_em; ++k) {
+        if (m.em_len[k] < 0 || m.em_off[k] < 0 || m.em_param[k] < -1 || m.em_param[k] >= m.n_params) return WFSA_OK;
+        n_bytes = std::max(n_bytes, m.em_off[k] + m.em_len[k]);
+    }
+    if (n_bytes > 0 && !m.em_bytes) return WFSA_OK;
+    for (int64_t k = 0; k < n_tr; ++k)
+        if (m.tr_dst[k] < 0 || m.tr_dst[k] >= N || m.tr_param[k] < -1 || m.tr_param[k] >= m.n_params) return WFSA_OK;
+    hipStream_t s = ctx->stream;
+    HIP_TRY(ctx->gn_em_ptr.upload(m.em_ptr, size_t(N) + 1, s));
+    HIP_TRY(ctx->gn_em_off.upload(m.em_off, size_t(n_em), s));
+    HIP_TRY(ctx->gn_em_len.upload(m.em_len, size_t(n_em), s));
+    HIP_TRY(ctx->gn_em_param.upload(m.em_param, size_t(n_em), s));
+    HIP_TRY(ctx->gn_em_bytes.upload(m.em_bytes, size_t(n_bytes), s));
+    HIP_TRY(ctx->gn_tr_ptr.upload(m.tr_ptr, size_t(N) + 1, s));
+    HIP_TRY(ctx->gn_tr_dst.upload(m.tr_dst, size_t(n_tr), s));
+    HIP_TRY(ctx->gn_tr_param.upload(m.tr_param, size_t(n_tr), s));
+    HIP_TRY(hipStreamSynchronize(s));   // (the description's arrays are the caller's)
+    ctx->gn_states = N;
+    ctx->gn_start = m.start;
+    ctx->gn_end = m.end;
+    ctx->gn_params = m.n_params;
+    ctx->gn_n_em = n_em;
+    ctx->gn_n_tr = n_tr;
+    *ok = true;
     return WFSA_OK;
 }
 
@@ -3259,6 +3326,8 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     for (DecodeBufs* d : {&ctx->bp, &ctx->kb, &ctx->sp, &ctx->pc, &ctx->bm})
         for (hipEvent_t ev : {d->ev0, d->ev1})
             if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : ctx->gn_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
             if (ev) (void)hipEventDestroy(ev);
@@ -3284,9 +3353,17 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
     ctx->dense_struct = false;
     ctx->stats.dense = 0;
     ctx->stats.dense_rows = ctx->stats.dense_steps = ctx->stats.dense_np = 0;
+    // generation walks the state graph itself: it goes up before the dense
+    // branch returns, so a model on the dense path can be generated from too
+    bool gn_uploaded = false;
+    if (int rc = upload_generate_graph(ctx, *model, &gn_uploaded)) return rc;
     if (ctx->dense_mode != 0) {
         wfsa::DenseModel dm;
-        if (wfsa::dense_model_build(*model, ctx->dense_mode == 1, dm).empty()) return load_dense_model(ctx, dm);
+        if (wfsa::dense_model_build(*model, ctx->dense_mode == 1, dm).empty()) {
+            const int rc = load_dense_model(ctx, dm);
+            ctx->gn_ready = rc == WFSA_OK && gn_uploaded;
+            return rc;
+        }
     }
     wfsa::TrellisModel tm;
     const std::string err = wfsa::compile_trellis_model(*model, tm);
@@ -3383,6 +3460,7 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
     ctx->stats.n_edges = ctx->n_edges;
     ctx->stats.n_end_edges = ctx->n_end;
     ctx->prep_level = 0;
+    ctx->gn_ready = gn_uploaded;
     if (ctx->has_corpus) return configure_tiers(ctx);
     return WFSA_OK;
 }
@@ -4904,6 +4982,142 @@ int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_
     if (logw && !ctx->sp_logw.empty()) std::memcpy(logw, ctx->sp_logw.data(), ctx->sp_logw.size() * sizeof(double));
     if (prow) std::memcpy(prow, ctx->sp_prow.data(), ctx->sp_prow.size() * sizeof(int64_t));
     if (pidx && !ctx->sp_pidx.empty()) std::memcpy(pidx, ctx->sp_pidx.data(), ctx->sp_pidx.size() * sizeof(int32_t));
+    return WFSA_OK;
+}
+
+// Unconditional generation (generate.hpp): n walks of the automaton itself.
+// Needs a model only -- the state graph that went up with it -- and buffers of
+// its own.  The running sums and the weights' check first; then the walk once
+// to size the outputs, a scan, and the walk again to fill them.
+int wfsa_dev_generate(wfsa_dev* ctx, const double* w_full, int64_t n, int32_t max_len, uint64_t seed, int64_t* total_bytes,
+                      int64_t* n_entries, int64_t status_counts[3]) {
+    const char* name = "generate";
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to walk", name);
+    if (!ctx->has_model || !ctx->gn_ready) return fail(WFSA_ERR_ARG, "%s: load a model first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (n < 1) return fail(WFSA_ERR_ARG, "%s: n = %lld is below 1", name, (long long)n);
+    if (max_len < 0) return fail(WFSA_ERR_ARG, "%s: max_len = %d is negative", name, int(max_len));
+    const int64_t max_steps = int64_t(ctx->gn_states) * (int64_t(max_len) + 1);
+    if (2 * max_steps >= (int64_t(1) << 32))
+        return fail(WFSA_ERR_ARG, "%s: %d states at max_len = %d allow %lld draws per sample, past the 32-bit draw index", name,
+                    ctx->gn_states, int(max_len), (long long)(2 * max_steps));
+    const int32_t np = ctx->gn_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    if (n >= (int64_t(1) << 31)) return fail(WFSA_ERR_CAPACITY, "%s: n = %lld samples exceed the per-sample tables", name, (long long)n);
+    ctx->gn_valid = false;
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& ev : ctx->gn_ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    const size_t N = size_t(n);
+    const int64_t tiles = wfsa::generate_tiles(n);
+    const unsigned zero = 0;
+    HIP_TRY(ctx->gn_w.upload(w_full, size_t(np), s));
+    HIP_TRY(ctx->gn_flag.upload(&zero, 1, s));
+    HIP_TRY(ctx->gn_cdf_tr.alloc(size_t(ctx->gn_n_tr)));
+    HIP_TRY(ctx->gn_cdf_em.alloc(size_t(ctx->gn_n_em)));
+    HIP_TRY(ctx->gn_len.alloc(N));
+    HIP_TRY(ctx->gn_plen.alloc(N));
+    HIP_TRY(ctx->gn_logw.alloc(N));
+    HIP_TRY(ctx->gn_logp.alloc(N));
+    HIP_TRY(ctx->gn_status.alloc(N));
+    HIP_TRY(ctx->gn_bsum.alloc(size_t(2 * tiles)));
+    HIP_TRY(ctx->gn_off.alloc(N + 1));
+    HIP_TRY(ctx->gn_prow.alloc(N + 1));
+    wfsa::GenerateArgs a{};
+    a.g.em_ptr = ctx->gn_em_ptr.ptr;
+    a.g.em_off = ctx->gn_em_off.ptr;
+    a.g.em_len = ctx->gn_em_len.ptr;
+    a.g.em_param = ctx->gn_em_param.ptr;
+    a.g.em_bytes = ctx->gn_em_bytes.ptr;
+    a.g.tr_ptr = ctx->gn_tr_ptr.ptr;
+    a.g.tr_dst = ctx->gn_tr_dst.ptr;
+    a.g.tr_param = ctx->gn_tr_param.ptr;
+    a.g.n_states = ctx->gn_states;
+    a.g.start = ctx->gn_start;
+    a.g.end = ctx->gn_end;
+    a.g.n_params = np;
+    a.w = ctx->gn_w.ptr;
+    a.cdf_tr = ctx->gn_cdf_tr.ptr;
+    a.cdf_em = ctx->gn_cdf_em.ptr;
+    a.flag = ctx->gn_flag.ptr;
+    a.n = n;
+    a.max_len = max_len;
+    a.max_steps = uint32_t(max_steps);
+    a.seed = seed;
+    a.len = ctx->gn_len.ptr;
+    a.plen = ctx->gn_plen.ptr;
+    a.logw = ctx->gn_logw.ptr;
+    a.logp = ctx->gn_logp.ptr;
+    a.status = ctx->gn_status.ptr;
+    a.bsum = ctx->gn_bsum.ptr;
+    a.off = ctx->gn_off.ptr;
+    a.prow = ctx->gn_prow.ptr;
+    unsigned flag = 0;
+    HIP_TRY(hipEventRecord(ctx->gn_ev[0], s));
+    HIP_TRY(wfsa::launch_generate_cdf(a, s));
+    HIP_TRY(ctx->gn_flag.download(&flag, 1, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (flag) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
+    HIP_TRY(wfsa::launch_generate_size(a, s));
+    HIP_TRY(hipEventRecord(ctx->gn_ev[1], s));
+    int64_t bytes = 0, ids = 0;
+    HIP_TRY(hipMemcpyAsync(&bytes, ctx->gn_off.ptr + N, sizeof bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&ids, ctx->gn_prow.ptr + N, sizeof ids, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bytes < 0 || ids < 0 || bytes > (int64_t(1) << 32) || ids * 4 > (int64_t(1) << 32))
+        return fail(WFSA_ERR_CAPACITY, "%s: %lld bytes and %lld path entries exceed 4 GiB; generate fewer samples per call", name,
+                    (long long)bytes, (long long)ids);
+    HIP_TRY(ctx->gn_sym.alloc(size_t(bytes)));
+    HIP_TRY(ctx->gn_pidx.alloc(size_t(ids)));
+    a.sym = ctx->gn_sym.ptr;
+    a.pidx = ctx->gn_pidx.ptr;
+    HIP_TRY(hipEventRecord(ctx->gn_ev[2], s));
+    HIP_TRY(wfsa::launch_generate_fill(a, s));
+    HIP_TRY(hipEventRecord(ctx->gn_ev[3], s));
+    ctx->gn_h_sym.resize(size_t(bytes));
+    ctx->gn_h_pidx.resize(size_t(ids));
+    ctx->gn_h_off.resize(N + 1);
+    ctx->gn_h_prow.resize(N + 1);
+    ctx->gn_h_logw.resize(N);
+    ctx->gn_h_logp.resize(N);
+    ctx->gn_h_status.resize(N);
+    HIP_TRY(ctx->gn_sym.download(ctx->gn_h_sym.data(), size_t(bytes), s));
+    HIP_TRY(ctx->gn_pidx.download(ctx->gn_h_pidx.data(), size_t(ids), s));
+    HIP_TRY(ctx->gn_off.download(ctx->gn_h_off.data(), N + 1, s));
+    HIP_TRY(ctx->gn_prow.download(ctx->gn_h_prow.data(), N + 1, s));
+    HIP_TRY(ctx->gn_logw.download(ctx->gn_h_logw.data(), N, s));
+    HIP_TRY(ctx->gn_logp.download(ctx->gn_h_logp.data(), N, s));
+    HIP_TRY(ctx->gn_status.download(ctx->gn_h_status.data(), N, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms0 = 0.f, ms1 = 0.f;   // (the host's look at the totals between the passes is not device time)
+    HIP_TRY(hipEventElapsedTime(&ms0, ctx->gn_ev[0], ctx->gn_ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms1, ctx->gn_ev[2], ctx->gn_ev[3]));
+    ctx->stats.generate_ms = double(ms0) + double(ms1);
+    int64_t counts[3] = {0, 0, 0};
+    for (int8_t st : ctx->gn_h_status) {
+        if (st < 0 || st > 2) return fail(WFSA_ERR_HIP, "%s: a walk left no status", name);
+        ++counts[st];
+    }
+    ctx->gn_valid = true;
+    if (total_bytes) *total_bytes = bytes;
+    if (n_entries) *n_entries = ids;
+    if (status_counts) std::memcpy(status_counts, counts, sizeof counts);
+    return WFSA_OK;
+}
+
+int wfsa_dev_generate_get(wfsa_dev* ctx, uint8_t* sym, int64_t* off, double* logw, double* logp, int8_t* status, int64_t* prow,
+                          int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->gn_valid) return fail(WFSA_ERR_ARG, "generate_get: no wfsa_dev_generate result since the last load");
+    const size_t N = ctx->gn_h_status.size();
+    if (sym && !ctx->gn_h_sym.empty()) std::memcpy(sym, ctx->gn_h_sym.data(), ctx->gn_h_sym.size());
+    if (off) std::memcpy(off, ctx->gn_h_off.data(), (N + 1) * sizeof(int64_t));
+    if (logw) std::memcpy(logw, ctx->gn_h_logw.data(), N * sizeof(double));
+    if (logp) std::memcpy(logp, ctx->gn_h_logp.data(), N * sizeof(double));
+    if (status) std::memcpy(status, ctx->gn_h_status.data(), N);
+    if (prow) std::memcpy(prow, ctx->gn_h_prow.data(), (N + 1) * sizeof(int64_t));
+    if (pidx && !ctx->gn_h_pidx.empty()) std::memcpy(pidx, ctx->gn_h_pidx.data(), ctx->gn_h_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
 

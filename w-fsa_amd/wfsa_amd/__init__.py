@@ -24,7 +24,7 @@ def _ptr(a):
 
 
 __all__ = ["Fsa", "Corpus", "QuasiNewtonLearner", "Device", "Synthetic", "WfsaError", "load", "shard_range",
-           "sym_sparse_solve", "trellis_stats", "sample_uniforms"]
+           "sym_sparse_solve", "trellis_stats", "sample_uniforms", "Generated"]
 
 
 def shard_range(off, nranks, rank):
@@ -106,6 +106,14 @@ class Fsa:
         d = _lib.ModelDesc()
         check_host(load().wfsa_fsa_desc(self._h, C.byref(d)))
         return d
+
+    def weights(self):
+        """the weights as read (log values) in parameter-index order: the
+        w_full of the automaton as it stands (wfsa_fsa_weights)"""
+        n = self.counts()["parameters"]
+        w = np.zeros(max(n, 1), dtype=np.float64)
+        check_host(load().wfsa_fsa_weights(self._h, _ptr(w)))
+        return w[:n]
 
     def param_name(self, j):
         s, k, l = C.c_char_p(), C.c_int32(), C.c_char_p()
@@ -189,6 +197,47 @@ class Synthetic:
         w_a = np.ctypeslib.as_array(C.cast(w, C.POINTER(C.c_double)), shape=(n,)).copy()
         sym_a = np.ctypeslib.as_array(C.cast(sym, C.POINTER(C.c_uint8)), shape=(int(off_a[-1]),)).copy()
         return sym_a, off_a, w_a
+
+
+class Generated(dict):
+    """what generate returns: sym, off, logw, logp, status, prow, pidx -- sample
+    i's bytes are sym[off[i]:off[i + 1]], its Fsa parameter ids in path order
+    pidx[prow[i]:prow[i + 1]], status 0 complete / 1 truncated / 2 dead"""
+
+    def strings(self):
+        """the samples' bytes, one bytes object each"""
+        sym, off = self["sym"].tobytes(), self["off"]
+        return [sym[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    def distinct(self):
+        """(sym, off, counts) of the distinct complete strings in
+        first-appearance order, ready for Device.load_corpus"""
+        seen = {}
+        for s, st in zip(self.strings(), self["status"]):
+            if st == 0:
+                seen[s] = seen.get(s, 0) + 1
+        off = np.zeros(len(seen) + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in seen], out=off[1:])
+        sym = np.frombuffer(b"".join(seen), dtype=np.uint8).copy()
+        return sym, off, np.array(list(seen.values()), dtype=np.float64)
+
+
+def _generate(call, get, check, head, n, max_len, seed):
+    """the generate call sequence, shared by Device and the learners"""
+    n = int(n)
+    nb, m = C.c_int64(), C.c_int64()
+    counts = np.zeros(3, dtype=np.int64)
+    check(call(*head, n, int(max_len), int(seed), C.byref(nb), C.byref(m), _ptr(counts)))
+    sym = np.zeros(max(nb.value, 1), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.int64)
+    logw = np.zeros(n, dtype=np.float64)
+    logp = np.zeros(n, dtype=np.float64)
+    status = np.zeros(n, dtype=np.int8)
+    prow = np.zeros(n + 1, dtype=np.int64)
+    pidx = np.zeros(max(m.value, 1), dtype=np.int32)
+    check(get(head[0], _ptr(sym), _ptr(off), _ptr(logw), _ptr(logp), _ptr(status), _ptr(prow), _ptr(pidx)))
+    assert counts.tolist() == np.bincount(status, minlength=3).tolist()
+    return Generated(sym=sym[:nb.value], off=off, logw=logw, logp=logp, status=status, prow=prow, pidx=pidx[:m.value])
 
 
 class QuasiNewtonLearner:
@@ -343,6 +392,12 @@ class QuasiNewtonLearner:
         pidx = np.zeros(max(m.value, 1), dtype=np.int32)
         check_host(load().wfsa_learner_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
         return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
+
+    def Generate(self, n, max_len=255, seed=0):
+        """n strings drawn from the automaton itself at the current x, at most
+        max_len bytes each: a Generated dict (sym, off, logw, logp, status,
+        prow, pidx; Device.generate's layout), reproducible from `seed`"""
+        return _generate(load().wfsa_learner_generate, load().wfsa_learner_generate_get, check_host, (self._h,), n, max_len, seed)
 
     def PosteriorCounts(self):
         """the per-string E-step at the current x, per local recognized string:
@@ -679,6 +734,25 @@ class Device:
         pidx = np.zeros(max(m.value, 1), dtype=np.int32)
         check_dev(load().wfsa_dev_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
         return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
+
+    def generate(self, w_full, n, max_len=255, seed=0):
+        """n independent strings drawn from the loaded automaton itself at
+        w_full (no corpus needed; works on the dense path): each state chooses
+        among its transitions and among its emissions with probability
+        proportional to exp(weight), from `start` until a transition reaches
+        `end`.  Returns a Generated dict: sample i's bytes
+        sym[off[i]:off[i + 1]] (at most max_len), its Fsa parameter ids in path
+        order pidx[prow[i]:prow[i + 1]], logw[i] the path's log weight as the
+        decoders form it, logp[i] the log probability of the walk (logw when
+        every group sums to 1) and status[i]: 0 complete, 1 truncated at
+        max_len, 2 dead (a state without a choice of positive mass).  The same
+        weights, max_len and seed give the same bytes, and the first j samples
+        of an n result are the j result; .distinct() gives the distinct
+        complete strings with their counts for load_corpus"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        return _generate(load().wfsa_dev_generate, load().wfsa_dev_generate_get, check_dev, (self._h, _ptr(w)), n, max_len, seed)
 
     def posterior_counts(self, w_full):
         """the per-string E-step at w_full: (crow, cidx, cval, logq, entropy) --

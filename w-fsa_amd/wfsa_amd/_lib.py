@@ -55,6 +55,7 @@ class DevStats(C.Structure):
         ("sample_path_ms", dbl), ("posterior_count_ms", dbl), ("byte_marginal_ms", dbl),
         ("shaped_bubbles", i64), ("mixed_shape_waves", i64), ("small_bubbles_a", i64), ("small_bubbles_b", i64),
         ("big_bubbles", i64), ("max_bubble_nodes", i32), ("max_bubble_edges", i32),
+        ("generate_ms", dbl),
     ]
 
 
@@ -89,6 +90,8 @@ _SIGS = {
     "wfsa_dev_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_sample_paths": (C.c_int, [vp, vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
     "wfsa_dev_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
+    "wfsa_dev_generate": (C.c_int, [vp, vp, i64, C.c_int32, C.c_uint64, P(i64), P(i64), vp]),
+    "wfsa_dev_generate_get": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "wfsa_dev_posterior_counts": (C.c_int, [vp, vp, vp, vp, P(i64)]),
     "wfsa_dev_posterior_counts_get": (C.c_int, [vp, vp, vp, vp]),
     "wfsa_dev_byte_marginals": (C.c_int, [vp, vp, C.c_int32, vp, vp, vp, vp, P(i64), P(i64)]),
@@ -128,6 +131,7 @@ _SIGS = {
     "wfsa_fsa_free": (None, [vp]),
     "wfsa_fsa_desc": (C.c_int, [vp, P(ModelDesc)]),
     "wfsa_fsa_counts": (C.c_int, [vp, vp]),
+    "wfsa_fsa_weights": (C.c_int, [vp, vp]),
     "wfsa_fsa_state_name": (C.c_int, [vp, i32, P(C.c_char_p)]),
     "wfsa_fsa_param_name": (C.c_int, [vp, i32, P(C.c_char_p), P(i32), P(C.c_char_p)]),
     "wfsa_corpus_read_text": (C.c_int, [C.c_char_p, P(vp)]),
@@ -159,6 +163,8 @@ _SIGS = {
     "wfsa_learner_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_learner_sample_paths": (C.c_int, [vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
     "wfsa_learner_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
+    "wfsa_learner_generate": (C.c_int, [vp, i64, C.c_int32, C.c_uint64, P(i64), P(i64), vp]),
+    "wfsa_learner_generate_get": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "wfsa_learner_posterior_counts": (C.c_int, [vp, vp, vp, P(i64)]),
     "wfsa_learner_posterior_counts_get": (C.c_int, [vp, vp, vp, vp]),
     "wfsa_learner_byte_marginals": (C.c_int, [vp, C.c_int32, vp, vp, vp, vp, P(i64), P(i64)]),
