@@ -139,6 +139,9 @@ typedef struct {
     int32_t max_bubble_nodes;  /* nodes of the largest compiled bubble (at most 32; 0: no bubble) */
     int32_t max_bubble_edges;  /* edges of the compiled bubble with the most edges (at most 255; 0: no bubble) */
     double generate_ms;        /* last wfsa_dev_generate call: device time of its kernels */
+    /* last wfsa_dev_dense_best_paths call (its sum is best_path_ms): the table
+     * kernel, the T forward steps, the back-track kernel */
+    double dense_bp_tables_ms, dense_bp_forward_ms, dense_bp_backtrack_ms;
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -233,6 +236,58 @@ int wfsa_dev_rmin(wfsa_dev* ctx, double* rmin, int64_t* string_index);
  * WFSA_ERR_CAPACITY (no trellis is built there: load with WFSA_DENSE=0). */
 int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries);
 int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx);
+
+/* Viterbi decode on the dense path (stats.dense == 1), where no trellis is
+ * built and wfsa_dev_best_paths fails: the most probable accepting path of
+ * every loaded string at w_full by a (max, +) pass over the row slots of the
+ * dense path (dense_decode.hip).  Outputs in best_paths' layout and
+ * conventions: best_logw[s] (-inf without an accepting path of finite weight:
+ * a byte no state emits, an empty string without a ^ -> $ edge, every path
+ * crossing a -inf weight; NULL allowed), *n_entries (NULL allowed), and
+ * dense_best_paths_get's pidx[prow[s] .. prow[s + 1]): Fsa parameter ids in
+ * path order, repeats kept, a transition before the emission it leads to, the
+ * end transition last; single-member groups carry no id; a string without a
+ * path has an empty range; an empty string with a ^ -> $ edge has that edge
+ * as its path.
+ *
+ * Arithmetic, exactly.  Log tables come from w_full and the model's parameter
+ * codes directly (never log(exp(w))), a missing edge or padded state -inf, a
+ * single-member group 0.0: lA[S][T], its transpose lAT[T][S], lE[v][T], l0[T]
+ * (^ -> T), lend[T] (T -> $).  Forward, per row slot r and step t:
+ *   D_t[r][T] = l0[T] + lE[sym][T]                          where a string starts,
+ *   D_t[r][T] = max_S(D_{t-1}[r][S] + lA[S][T]) + lE[sym][T]  elsewhere
+ * (the max first, then one add); every D_t is kept -- T x R x np doubles,
+ * the size of one of the three histories of an evaluation, allocated by the
+ * first call and freed by the next load.  End: the T that maximises
+ * D_end[r][T] + lend[T], ties to the lowest T; a maximum of -inf: no path.
+ * Back-track: the predecessor of T is the S that maximises D_{t-1}[r][S] +
+ * lAT[T][S], ties to the lowest S, recomputed from the history (no
+ * back-pointers are stored); a -inf candidate is never chosen.
+ * best_logw is not the search's score but the decoders' weight of the
+ * returned path: an edge's weight is the left-to-right sum, from 0.0, of its
+ * present parameters' weights (transition, then emission), the path's the
+ * left-to-right sum, from 0.0, of its edges' weights, the end edge last -- bit
+ * for bit what best_paths / kbest_paths report for that path when the model
+ * is loaded with WFSA_DENSE=0.  The search rounds (D + lA) + lE where the
+ * trellis decode rounds D + (lA + lE), so the returned path can differ from
+ * best_paths' only where a decision on it is closer than that rounding (a
+ * few ulp) or at exact ties; there both break ties towards the lowest state
+ * (for a model that qualifies for the dense path best_paths' first in-edge is
+ * the one from the lowest source state).
+ *
+ * Needs a loaded model and corpus; no evaluation has to have run.  Local to
+ * the rank; leaves the learning path untouched (evaluations, rmin, the QN
+ * loop and generate go on as if it had not run).  Valid until the next load
+ * or dense_best_paths call.  stats.best_path_ms = device time of its kernels
+ * (dense_bp_*_ms its parts).  WFSA_ERR_ARG when the model is not on the dense
+ * path (use wfsa_dev_best_paths), before a model and a corpus are loaded, in
+ * matrix-file mode, while an evaluation is in flight, for a w_full entry that
+ * is NaN or +inf (before any kernel runs), and from _get without a result
+ * since the last load; WFSA_ERR_CAPACITY, naming the bytes, when the score
+ * history cannot be allocated. */
+int wfsa_dev_dense_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw /* [n_strings], NULL ok */,
+                              int64_t* n_entries /* NULL ok */);
+int wfsa_dev_dense_best_paths_get(wfsa_dev* ctx, int64_t* prow /* [n_strings + 1] */, int32_t* pidx /* [n_entries] */);
 
 /* K-best decode: the k most probable accepting paths of every loaded string at
  * w_full, 1 <= k <= WFSA_KBEST_MAX -- best_paths' trellis pass with a sorted

@@ -577,16 +577,22 @@ void Learner::BestPaths(double* best_logw, int64_t* n_entries) {
     if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
     const double none = 0.0;
     get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
-    const int rc = wfsa_dev_best_paths(dev, w_full.data(), best_logw, n_entries);
-    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_best_paths: ", wfsa_dev_last_error());
-    ThrowOnDevError(rc, "wfsa_dev_best_paths");
+    wfsa_dev_stats st;
+    ThrowOnDevError(wfsa_dev_get_stats(dev, &st), "wfsa_dev_get_stats");
+    best_paths_dense = st.dense != 0;   // no trellis there: the (max, +) pass over the row slots
+    const char* fn = best_paths_dense ? "wfsa_dev_dense_best_paths" : "wfsa_dev_best_paths";
+    const int rc = best_paths_dense ? wfsa_dev_dense_best_paths(dev, w_full.data(), best_logw, n_entries)
+                                    : wfsa_dev_best_paths(dev, w_full.data(), best_logw, n_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError(fn, ": ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, fn);
 }
 
 void Learner::BestPathsGet(int64_t* prow, int32_t* pidx) const {
     if (!dev) throw LearnerUsageError("BuildFrom has not run");
-    const int rc = wfsa_dev_best_paths_get(dev, prow, pidx);
-    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_best_paths_get: ", wfsa_dev_last_error());
-    ThrowOnDevError(rc, "wfsa_dev_best_paths_get");
+    const char* fn = best_paths_dense ? "wfsa_dev_dense_best_paths_get" : "wfsa_dev_best_paths_get";
+    const int rc = best_paths_dense ? wfsa_dev_dense_best_paths_get(dev, prow, pidx) : wfsa_dev_best_paths_get(dev, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError(fn, ": ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, fn);
 }
 
 void Learner::KBestPaths(int32_t k, int64_t* n_paths, int64_t* n_entries) {

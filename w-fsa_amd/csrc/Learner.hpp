@@ -142,7 +142,8 @@ public:
     // w_full): per local recognized string, in p's order, the log weight of its
     // best path; *n_entries = total length of the paths' parameter lists, which
     // BestPathsGet copies out (prow[n_local + 1], pidx: Fsa parameter ids in
-    // path order)
+    // path order).  A model on the dense path is decoded by
+    // wfsa_dev_dense_best_paths, same outputs
     void BestPaths(double* best_logw, int64_t* n_entries);
     void BestPathsGet(int64_t* prow, int32_t* pidx) const;
     // K-best decode at the current x (wfsa_dev_kbest_paths with GetWeight's
@@ -240,6 +241,7 @@ private:
     std::vector<uint8_t> recognized_local;
     bool logq_valid = false;
     bool eval_in_flight = false, eval_logq = false;
+    bool best_paths_dense = false;   // the last BestPaths ran the dense path's decoder
 
     int device = 0;
     wfsa_dev* dev = nullptr;

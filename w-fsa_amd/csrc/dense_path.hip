@@ -1217,6 +1217,9 @@ void DensePath::free_corpus() {
     dfree(la_); dfree(lb_); dfree(alpha_); dfree(gam_); dfree(z_); dfree(y_); dfree(ysplit_); dfree(part_);
     dfree(ll_part_); dfree(red_);
     dfree(lmat_); dfree(let_); dfree(l0_); dfree(lend_); dfree(mrow_); dfree(spart_); dfree(rpart_);
+    dfree(doff_); dfree(dw_); dfree(dla_); dfree(dlat_); dfree(dle_); dfree(dl0_); dfree(dlend_); dfree(dhist_);
+    dfree(dstates_); dfree(dcodes_); dfree(dlogw_);
+    off_host_.clear();
     n_strings_ = 0;
     R_ = T_ = 0;
     weighted_ = false;
@@ -1357,6 +1360,10 @@ hipError_t DensePath::load_corpus(const uint8_t* sym, const int64_t* off, const 
     DTRY(hipMemcpyAsync(meta_, meta.data(), TR * 4, hipMemcpyHostToDevice, s));
     DTRY(hipMemcpyAsync(sid_, sid.data(), TR * 4, hipMemcpyHostToDevice, s));
     DTRY(hipMemcpyAsync(end_at_, end_at.data(), S * 4, hipMemcpyHostToDevice, s));
+    off_host_.resize(S + 1);   // (the decode's, from 0: dense_decode.hip)
+    for (size_t i = 0; i <= S; ++i) off_host_[i] = off[i] - off[0];
+    DTRY(dalloc(doff_, S + 1));
+    DTRY(hipMemcpyAsync(doff_, off_host_.data(), (S + 1) * 8, hipMemcpyHostToDevice, s));
     if (S) DTRY(hipMemcpyAsync(p_, p, S * 8, hipMemcpyHostToDevice, s));
     std::vector<double> ones(std::max<size_t>(S, 1), 1.0);
     DTRY(hipMemcpyAsync(pones_, ones.data(), S * 8, hipMemcpyHostToDevice, s));

@@ -83,6 +83,23 @@ public:
     // fp64 VALU (a semiring MFMA does not compute).  Empty strings (one path,
     // relative probability 1) are not candidates.
     hipError_t enqueue_rmin(double* res, const unsigned* halted, hipStream_t s);
+    // Viterbi decode at w_full (host, n_params log weights of which -inf is
+    // the only non-finite value): a (max, +) pass over the same row slots
+    // that keeps every step's scores (T x R x np doubles, allocated by the
+    // first call since the load) and a back-track kernel that recomputes each
+    // predecessor from them, ties to the lowest state (dense_decode.hip).
+    // Buffers of its own: the evaluations' and the rmin pass's state is not
+    // touched.  ev[0..3] are recorded before the table kernel, after it,
+    // after the forward steps and after the back-track.
+    // hipErrorOutOfMemory: the history (best_paths_history_bytes) does not fit.
+    hipError_t enqueue_best_paths(const double* w_full, hipEvent_t const ev[4], hipStream_t s);
+    size_t best_paths_history_bytes() const;
+    // the last pass's results: logw[S] the paths' weights (-inf: no path) and
+    // codes[2 (total_symbols + S)]: string s owns the pairs from 2 (off[s] + s),
+    // one (transition code, emission code) per byte and (end code, kCodeOne)
+    // last; an empty string has its ^ -> $ code alone
+    hipError_t best_paths_download(double* logw, int32_t* codes, hipStream_t s) const;
+    const std::vector<int64_t>& string_offsets() const { return off_host_; }
 
     // the last evaluation ran at real weights (not the structural pass)
     bool weighted() const { return weighted_; }
@@ -166,6 +183,20 @@ private:
     double* mrow_ = nullptr;   // [2][R][np]
     double* spart_ = nullptr;  // [nct][S]
     double* rpart_ = nullptr;  // [2 * blocks]
+    // Viterbi decode (allocated by its first call, freed with the corpus):
+    // the weights, log tables (-inf: no edge), the score history, the paths
+    std::vector<int64_t> off_host_;   // [S + 1] the strings' offsets
+    int64_t* doff_ = nullptr;  // [S + 1]
+    double* dw_ = nullptr;     // [n_params]
+    double* dla_ = nullptr;    // [np][np] log A
+    double* dlat_ = nullptr;   // [np][np] transposed
+    double* dle_ = nullptr;    // [vocab+1][np] log E^T
+    double* dl0_ = nullptr;    // [np]
+    double* dlend_ = nullptr;  // [np]
+    double* dhist_ = nullptr;  // [T][R][np]
+    int32_t* dstates_ = nullptr;  // [total symbols]
+    int32_t* dcodes_ = nullptr;   // [2 (total symbols + S)]
+    double* dlogw_ = nullptr;  // [S]
     hipError_t enqueue_lib(const double* w, const double* p, bool structural, double* out, double* logq,
                            const unsigned* halted, hipStream_t s);
     void free_corpus();

@@ -490,6 +490,12 @@ struct wfsa_dev {
     std::vector<double> bm_mval;
     std::vector<int64_t> bp_prow;
     std::vector<int32_t> bp_pidx;
+    // the dense path's Viterbi decode (wfsa_dev_dense_best_paths): its last
+    // result for _get, in best_paths_get's layout, and its four timing events
+    bool dbp_valid = false;
+    std::vector<int64_t> dbp_prow;
+    std::vector<int32_t> dbp_pidx;
+    hipEvent_t dbp_ev[4] = {};
     // Unconditional generation (wfsa_dev_generate; generate.hpp): the flattened
     // state graph as wfsa_model_desc gives it (uploaded with the model, on the
     // dense path too), the call's weights and running sums, the per-sample
@@ -3131,7 +3137,8 @@ void drop_graph(wfsa_dev* ctx) {
 void invalidate_decodes(wfsa_dev* ctx) {
     ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = ctx->pc.valid = ctx->bm.valid = false;
     ctx->gn_valid = false;
-    ctx->bm_base_ok = false;   // (the state sums' addresses belong to one model and one corpus)
+    ctx->dbp_valid = false;
+    ctx->bm_base_ok = false;  // (the state sums' addresses belong to one model and one corpus)
 }
 
 // weights in / results out, sized by n_params
@@ -3327,6 +3334,8 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
         for (hipEvent_t ev : {d->ev0, d->ev1})
             if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->gn_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : ctx->dbp_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
@@ -4817,6 +4826,71 @@ int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
     if (!ctx->bp.valid) return fail(WFSA_ERR_ARG, "best_paths_get: no wfsa_dev_best_paths result since the last load");
     if (prow) std::memcpy(prow, ctx->bp_prow.data(), ctx->bp_prow.size() * sizeof(int64_t));
     if (pidx && !ctx->bp_pidx.empty()) std::memcpy(pidx, ctx->bp_pidx.data(), ctx->bp_pidx.size() * sizeof(int32_t));
+    return WFSA_OK;
+}
+
+// Viterbi decode on the dense path: the (max, +) pass over the row slots and
+// its back-track (DensePath::enqueue_best_paths), then the paths' parameter
+// codes filtered to Fsa parameter ids on the host
+int wfsa_dev_dense_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries) {
+    const char* name = "dense_best_paths";
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to decode over", name);
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (!ctx->dense)
+        return fail(WFSA_ERR_ARG, "%s: the model is not on the dense path; decode it with wfsa_dev_best_paths", name);
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    for (int32_t j = 0; j < np; ++j)   // (-inf is the only non-finite value the pass may meet)
+        if (std::isnan(w_full[j]) || w_full[j] == INFINITY) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
+    ctx->dbp_valid = false;
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& ev : ctx->dbp_ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    const hipError_t e = ctx->dense->enqueue_best_paths(w_full, ctx->dbp_ev, s);
+    if (e == hipErrorOutOfMemory)
+        return fail(WFSA_ERR_CAPACITY, "%s: the score history of %lld bytes (%d steps x %d row slots x %d states) cannot be allocated", name,
+                    (long long)ctx->dense->best_paths_history_bytes(), ctx->dense->steps(), ctx->dense->rows(), ctx->dense->np());
+    HIP_TRY(e);
+    const int64_t S = ctx->n_strings;
+    const std::vector<int64_t>& off = ctx->dense->string_offsets();
+    std::vector<double> logw(size_t(S), 0.0);
+    std::vector<int32_t> codes(2 * size_t(off[size_t(S)] + S), wfsa::kCodeNone);
+    HIP_TRY(ctx->dense->best_paths_download(logw.data(), codes.data(), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms[3] = {0.f, 0.f, 0.f};
+    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ctx->dbp_ev[i], ctx->dbp_ev[i + 1]));
+    ctx->stats.dense_bp_tables_ms = double(ms[0]);
+    ctx->stats.dense_bp_forward_ms = double(ms[1]);
+    ctx->stats.dense_bp_backtrack_ms = double(ms[2]);
+    ctx->stats.best_path_ms = double(ms[0]) + double(ms[1]) + double(ms[2]);
+    ctx->dbp_prow.assign(size_t(S) + 1, 0);
+    ctx->dbp_pidx.clear();
+    for (int64_t i = 0; i < S; ++i) {
+        if (logw[size_t(i)] > -INFINITY) {
+            const int32_t* cd = codes.data() + 2 * (off[size_t(i)] + i);
+            const int64_t n = 2 * (off[size_t(i) + 1] - off[size_t(i)] + 1);
+            for (int64_t q = 0; q < n; ++q) {
+                if (cd[q] == wfsa::kCodeNone || cd[q] >= np)
+                    return fail(WFSA_ERR_HIP, "%s: string %lld: code %d at entry %lld is not a path edge", name, (long long)i, int(cd[q]),
+                                (long long)q);
+                if (cd[q] >= 0) ctx->dbp_pidx.push_back(cd[q]);
+            }
+        }
+        ctx->dbp_prow[size_t(i) + 1] = int64_t(ctx->dbp_pidx.size());
+    }
+    if (best_logw && S > 0) std::memcpy(best_logw, logw.data(), size_t(S) * sizeof(double));
+    ctx->dbp_valid = true;
+    if (n_entries) *n_entries = int64_t(ctx->dbp_pidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_dense_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->dbp_valid) return fail(WFSA_ERR_ARG, "dense_best_paths_get: no wfsa_dev_dense_best_paths result since the last load");
+    if (prow) std::memcpy(prow, ctx->dbp_prow.data(), ctx->dbp_prow.size() * sizeof(int64_t));
+    if (pidx && !ctx->dbp_pidx.empty()) std::memcpy(pidx, ctx->dbp_pidx.data(), ctx->dbp_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
 

@@ -694,6 +694,21 @@ class Device:
         check_dev(load().wfsa_dev_best_paths_get(self._h, _ptr(prow), _ptr(pidx)))
         return logw, prow, pidx[:n.value]
 
+    def dense_best_paths(self, w_full):
+        """Viterbi decode of a model on the dense path (stats()["dense"] == 1),
+        where best_paths has no trellis to walk: (logw, prow, pidx) in
+        best_paths' layout, from a (max, +) pass over the dense row slots"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        logw = np.zeros(self.n_strings, dtype=np.float64)
+        n = C.c_int64()
+        check_dev(load().wfsa_dev_dense_best_paths(self._h, _ptr(w), _ptr(logw), C.byref(n)))
+        prow = np.zeros(self.n_strings + 1, dtype=np.int64)
+        pidx = np.zeros(max(n.value, 1), dtype=np.int32)
+        check_dev(load().wfsa_dev_dense_best_paths_get(self._h, _ptr(prow), _ptr(pidx)))
+        return logw, prow, pidx[:n.value]
+
     def kbest_paths(self, w_full, k):
         """K-best decode of every loaded string at w_full, 1 <= k <= 16:
         (srow, logw, prow, pidx) -- string s owns the paths srow[s]:srow[s + 1]

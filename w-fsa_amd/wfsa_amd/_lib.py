@@ -56,6 +56,7 @@ class DevStats(C.Structure):
         ("shaped_bubbles", i64), ("mixed_shape_waves", i64), ("small_bubbles_a", i64), ("small_bubbles_b", i64),
         ("big_bubbles", i64), ("max_bubble_nodes", i32), ("max_bubble_edges", i32),
         ("generate_ms", dbl),
+        ("dense_bp_tables_ms", dbl), ("dense_bp_forward_ms", dbl), ("dense_bp_backtrack_ms", dbl),
     ]
 
 
@@ -86,6 +87,8 @@ _SIGS = {
     "wfsa_dev_rmin": (C.c_int, [vp, vp, vp]),
     "wfsa_dev_best_paths": (C.c_int, [vp, vp, vp, P(i64)]),
     "wfsa_dev_best_paths_get": (C.c_int, [vp, vp, vp]),
+    "wfsa_dev_dense_best_paths": (C.c_int, [vp, vp, vp, P(i64)]),
+    "wfsa_dev_dense_best_paths_get": (C.c_int, [vp, vp, vp]),
     "wfsa_dev_kbest_paths": (C.c_int, [vp, vp, C.c_int32, P(i64), P(i64)]),
     "wfsa_dev_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_sample_paths": (C.c_int, [vp, vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
