@@ -585,6 +585,10 @@ int wfsa_dev_string_tiers(wfsa_dev* ctx, int8_t* tier);
  *   *loglik        = sum_s p_s log q_s
  *   grad_full[j]   = -sum_s p_s E_{path|s}[count_j]   (NULL allowed)
  *   logq[s]        = log q_s for the loaded strings     (NULL allowed)
+ * A loaded string without an accepting path has logq[s] = -inf and makes
+ * loglik -inf when p_s > 0; on the dense path it adds nothing to grad_full
+ * either way and, with p_s = 0, nothing to loglik, and it does not disturb
+ * the string packed behind it in its row slot.
  * With a communicator attached, loglik and grad_full are summed over ranks
  * (one RCCL all-reduce) and logq stays local. */
 int wfsa_dev_objective_grad(wfsa_dev* ctx, const double* w_full, double* loglik,
