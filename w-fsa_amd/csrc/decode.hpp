@@ -28,7 +28,17 @@
 //
 // The order on a node's paths is (weight descending, in-edge ascending, source
 // rank ascending); at the end (weight descending, live slot ascending, end edge
-// ascending, rank ascending).  It is total and defined without reference to K,
+// ascending, rank ascending).  "In-edge" is the index into w.e_src / w.e_g,
+// which runs through the lists of all bytes; a destination's candidates all
+// come from its own e_ptr range of one byte's list, so what decides is the
+// order within that range: source node ascending, then the source's out-edge
+// order (the table's stable sort by destination).  Nodes are numbered as the
+// model description numbers its states (Fsa's container order, not the
+// file's), the chain nodes behind them.  "End edge" is the index x of x_ptr,
+// which runs through the nodes in ascending order, and the live slots ascend
+// by node, so (live slot, end edge) is the end edges' own order.  A source
+// rank is compared only behind an equal in-edge, i.e. within one source's list.
+// The order is total and defined without reference to K,
 // and a path's weight is one left-to-right sum, so the first j paths of a K
 // result are the j result bit for bit, and the first path is the Viterbi
 // decode's.  A lane therefore merges into a compile-time capacity KC >= K (2,

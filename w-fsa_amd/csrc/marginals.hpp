@@ -50,6 +50,10 @@
 //   at the end by (score descending, node ascending) over the live nodes that
 //   have a finite end edge, then that node's end edges by (lw descending, end
 //   edge ascending).
+// (e and the end edge as decode.hpp defines them: within a destination's e_ptr
+// range source node ascending, then the source's out-edge order; the scores
+// compared are the sums of the state sums as stored, so two paths that tie in
+// exact arithmetic are ordered by the stored words.)
 // Lane 0 walks the back-pointers and writes the path's L + 1 combined edge ids,
 // as the Viterbi decoder does, and forms the path's log weight as the decoders
 // do: one left-to-right sum of lw, so the path carries bit for bit the weight
