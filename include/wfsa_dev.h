@@ -142,6 +142,7 @@ typedef struct {
     /* last wfsa_dev_dense_best_paths call (its sum is best_path_ms): the table
      * kernel, the T forward steps, the back-track kernel */
     double dense_bp_tables_ms, dense_bp_forward_ms, dense_bp_backtrack_ms;
+    int64_t qn_wave_launches;  /* QN steps so far whose update ran as qn_wave_kernel, a wave per constraint (WFSA_QN_WAVE=0: none; the others launch qn_step_kernel or ride in the stream kernel) */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */

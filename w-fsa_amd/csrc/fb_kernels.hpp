@@ -919,6 +919,11 @@ hipError_t launch_stage(const double* host_w, double* w, double* ewp, int32_t n,
 // fused: the member gradients include the bubble slot sums (every constraint
 // has at most kQnMaxSeg members); grid max(k, 1)
 hipError_t launch_qn_step(const QnArgs& a, bool fused, hipStream_t stream);
+// the fused update a wave per constraint instead of a block (qn_wave_kernel, qn_kernel.hip; the same bits): every
+// constraint with 1 to kQnWaveMembers members and at most kQnWaveMaxChunks slot chunks, a.contrib and a.fixed_t
+// set, no rmin strings pass folded in (a.rm_on) and no a.ll_stash; grid ceil(k / 4)
+constexpr int kQnWaveMaxChunks = 64 * kQnWaveChunkRounds;
+hipError_t launch_qn_wave(const QnArgs& a, hipStream_t stream);
 // dst[i] = src[idx[i]], i < n
 hipError_t launch_gather(const double* src, const int32_t* idx, int32_t n, double* dst, hipStream_t stream);
 // a step's finish as its own one-block launch

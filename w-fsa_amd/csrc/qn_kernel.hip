@@ -3,7 +3,8 @@
 // with ComputeExpX :53-56, ComputeG :148-160, ComputeLambdaNext :127-146,
 // Learner::LambdaUpdate src/Learner.cpp:438-462, HaltCondition :88-91 and
 // GetOptimizationInfo :68-86) after the objective/gradient kernels of the
-// same step, in ONE launch: qn_step_kernel, one block per constraint; the
+// same step, in ONE launch: qn_step_kernel, one block per constraint (or, for
+// the fused step whose constraints fit a wave, qn_wave_kernel below); the
 // step's finish (qn_finish, qn_device.hpp: the info row, the halt decision)
 // runs in the first block of the next step's stream kernel, or as a
 // one-block launch (fb_kernels.hpp, QnFinish).  It keeps x, lambda and the
@@ -233,6 +234,138 @@ __global__ __launch_bounds__(NT) void qn_step_kernel(QnArgs a) {
     }
 }
 
+// The fused step's update with a wave per constraint: qn_step_kernel<true>'s
+// arithmetic, operation for operation and in its summation orders, for
+// constraints of at most kQnWaveMembers members and kQnWaveMaxChunks slot
+// chunks (launch_qn_wave; the host's path rule).  A lane per member; the
+// chunk sums (eight lanes a chunk, chunk_tree's order, the partners' values
+// by DPP moves), the members' exp(x) and gradients pass through the wave's
+// own LDS rows, which only that wave touches -- no __syncthreads, nothing
+// that waits on another wave.  Every lane then runs ComputeG and
+// ComputeLambdaNext itself from LDS broadcasts (the same member-order sums on
+// every lane), so nothing is broadcast back.  A block is four such waves.
+constexpr int kQnWaveLds = kQnWaveMaxChunks + 2 * kQnWaveMembers;   // doubles per wave
+__device__ __forceinline__ void qn_wave_sync() {   // (LDS is processed in issue order for one wave: a compiler fence)
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
+template <int CTRL>
+__device__ __forceinline__ double qn_dpp(double v) {   // v of the lane CTRL names (a DPP control)
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__global__ __launch_bounds__(kQnBlock) void qn_wave_kernel(QnArgs a) {
+    if (WFSA_KDBG(a.dbg) == 3) return;   // (timing experiments: the launch alone)
+    __shared__ __attribute__((aligned(16))) double wlds[kQnBlock / 64][kQnWaveLds];
+    const int lane = int(threadIdx.x) & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
+    const int c = int(blockIdx.x) * (kQnBlock / 64) + wv;
+    // halted and halt_pending are written only by earlier launches
+    const unsigned h0 = a.halted[0], h1 = a.halted[1];
+    if (c >= a.k) return;   // (the last block's spare waves)
+    const int b = a.cptr[c], e = a.cptr[c + 1];
+    const double lam = a.lambda[c];
+    const int64_t gb = a.grp_base[c];
+    const int gnch = WFSA_KDBG(a.dbg) == 5 ? 0 : a.grp_nch[c];   // (5: timing experiments, no slot loads)
+    if (h0 || h1) {   // a step enqueued after the halt: published as skipped
+        if (c == 0 && lane == 0) {
+            a.halted[0] = 1u;   // for the evaluation kernels of the later steps
+            qn_publish_row(a.fin, nullptr, kQnSkipped);
+        }
+        return;
+    }
+    double* cp = wlds[wv];
+    double* se = cp + kQnWaveMaxChunks;
+    double* sg = se + kQnWaveMembers;
+    const int nm = min(e - b, kQnWaveMembers);   // (the path rule guarantees both bounds: the wave's LDS rows)
+    const int gn = min(gnch, kQnWaveMaxChunks);
+    const bool valid = lane < nm;
+    const int i = b + (valid ? lane : 0);   // (idle lanes read member 0: no branch around the loads)
+    const double x = a.x[i], ft = a.fixed_t[i];
+    const int fo = a.full_of[i];
+    const int q0a = a.chunk_ptr[i], q1a = a.chunk_ptr[i + 1];
+    const double gout = a.use_out ? a.out[1 + fo] : 0.0;
+    if (WFSA_KDBG(a.dbg) == 1) {   // (timing experiments: the launch and the member loads, kept alive)
+        if (x + ft + gout + double(q0a + q1a) == 0.12345) a.partial[0] = lam + double(gb + gn);
+        return;
+    }
+    // the group's chunk sums: a wave reads 8 chunks per load (lane: chunk
+    // lane / 8, piece lane % 8) and reduces each in chunk_tree's order
+    const double2* v2 = reinterpret_cast<const double2*>(a.contrib + gb);
+    const int sub = lane & 7;
+    for (int cb0 = 0; cb0 < gn; cb0 += 64) {
+        double2 y[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int q = cb0 + 8 * r + (lane >> 3);
+            y[r] = q < gn ? v2[size_t(q) * 8 + sub] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            double sr = y[r].x + y[r].y;
+            sr += qn_dpp<0xB1>(sr);    // lane ^ 1 (quad_perm 1,0,3,2)
+            sr += qn_dpp<0x4E>(sr);    // lane ^ 2 (quad_perm 2,3,0,1)
+            sr += qn_dpp<0x141>(sr);   // the other quad of the eight (row_half_mirror; its lanes hold one value)
+            const int q = cb0 + 8 * r + (lane >> 3);
+            if (sub == 0 && q < gn) cp[q] = sr;
+        }
+    }
+    qn_wave_sync();
+    // each member its chunk sums, in chunk order
+    const int c0 = __builtin_amdgcn_readfirstlane(q0a);   // (lane 0 is member 0)
+    double sm = 0.0;
+    if (valid) {
+        int q = q0a - c0;
+        const int q1 = min(q1a - c0, gn);
+        for (; q + 8 <= q1; q += 8) {
+            double t[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t[k] = cp[q + k];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sm += t[k];
+        }
+        for (; q < q1; ++q) sm += cp[q];
+    }
+    double gi = gout;   // the traversal part, + the trivial words', + the slots'
+    gi += ft;
+    gi = gi + sm;
+    const double ei = exp(x);
+    if (valid) {
+        se[lane] = ei;
+        sg[lane] = gi;
+    }
+    qn_wave_sync();
+    double gg = -1.0;   // ComputeG, ComputeLambdaNext in member order (on every lane alike)
+    for (int m = 0; m < nm; ++m) gg += se[m];
+    double r = lam * gg;
+    for (int m = 0; m < nm; ++m) r -= sg[m];
+    const double laux = r / (gg + 1.0);
+    double gerr = 0.0;
+    if (valid) {   // graderr (old lambda), x update (lambda_next)
+        const double aux = ei * lam;
+        gerr = fmax(gerr, fabs(gi + aux));
+        const double xn = x - a.eta * ((gi + ei * laux) / aux);
+        a.x[i] = xn;
+        a.grad[i] = gi;
+        a.w_full[fo] = xn;   // GetWeight for the next step
+        a.ewp[fo] = exp(xn);
+    }
+    gerr = wave_reduce(gerr, 1);   // (max is exact in any order)
+    if (lane == 0) {   // LambdaUpdate (src/Learner.cpp:438-462), and the partial for the step's finish
+        const double d = lam - laux;
+        a.lambda[c] = a.exp_lambda ? lam * exp(-a.eta * (d / lam)) : lam - a.eta * d;
+        double4 pv;
+        pv.x = gg;
+        pv.y = gg;
+        pv.z = lam;
+        pv.w = gerr;
+        reinterpret_cast<double4*>(a.partial)[c] = pv;
+    }
+}
+
 template <bool PX>
 __global__ __launch_bounds__(kQnBlock) void qn_finish_kernel(QnFinish f) {
     if (f.halted[0] || f.halted[1]) return;   // the step was skipped (and published so)
@@ -271,6 +404,16 @@ hipError_t launch_qn_step(const QnArgs& a_in, bool fused, hipStream_t stream) {
     }
     if (fused) hipLaunchKernelGGL((qn_step_kernel<true>), grid, dim3(kQnBlock), lds, stream, a);
     else hipLaunchKernelGGL((qn_step_kernel<false>), grid, dim3(kQnBlock), lds, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_qn_wave(const QnArgs& a_in, hipStream_t stream) {
+    static const int dbg = experiment_knob("WFSA_QN_DBG");
+    if (a_in.k <= 0 || !a_in.contrib || !a_in.fixed_t || a_in.rm_on || a_in.ll_stash) return hipErrorInvalidValue;
+    QnArgs a = a_in;
+    a.dbg = dbg;
+    constexpr int WPB = kQnBlock / 64;
+    hipLaunchKernelGGL(qn_wave_kernel, dim3(unsigned((a.k + WPB - 1) / WPB)), dim3(kQnBlock), 0, stream, a);
     return hipGetLastError();
 }
 

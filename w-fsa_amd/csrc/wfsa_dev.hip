@@ -418,6 +418,10 @@ struct wfsa_dev {
                                      // WFSA_BUBBLE_SHAPES=0: every id 0, the generic sweeps)
     uint64_t qw_seq = 0;             // in-kernel QN launches enqueued (their parity)
     wfsa::QnWave qw_next{};          // picked up by the next stream kernel launch (qw_next.on)
+    // the two-kernel step's QN update a wave per constraint (qn_wave_kernel,
+    // qn_kernel.hip) instead of qn_step_kernel's block per constraint
+    bool use_qn_wave = true;         // WFSA_QN_WAVE=0: qn_step_kernel
+    bool qnw_ok = false;             // this Run: every constraint fits a wave (qn_run_impl)
     DevBuf<unsigned long long> fbs_trace;   // timing experiments (WFSA_FBS_TRACE): per-wave stamps of the last launch
 
     // dense automata: the fp64 MFMA path (dense_path.hpp) replaces the
@@ -3097,7 +3101,20 @@ int enqueue_qn_step(wfsa_dev* ctx, double eta, double tol, int64_t e, bool timed
             return rc;
         }
     }
-    if (!inkern) HIP_TRY(wfsa::launch_qn_step(q, fused, s));
+    // The update as its own kernel: a wave per constraint (qn_wave_kernel)
+    // for the fused one-rank step whose constraints all fit one wave (qnw_ok)
+    // and whose QN blocks carry no rmin strings pass;
+    // with no bubble slots qn_step_kernel adds no slot sum at all (a -0.0
+    // gradient stays -0.0), so that step stays there too.  Else
+    // qn_step_kernel, a block per constraint.
+    const bool wave = !inkern && fused && ctx->use_qn_wave && ctx->qnw_ok && ctx->fixed_t_on && !q.rm_on &&
+                      q.contrib != nullptr && !q.ll_stash;
+    if (wave) {
+        HIP_TRY(wfsa::launch_qn_wave(q, s));
+        ++ctx->stats.qn_wave_launches;
+    } else if (!inkern) {
+        HIP_TRY(wfsa::launch_qn_step(q, fused, s));
+    }
     // the finish reads the step's log-likelihood partials: it can ride in the
     // next step's stream kernel when those are not in `out` (which that
     // kernel zeroes); else it is launched when the next step is enqueued
@@ -3294,6 +3311,7 @@ int wfsa_dev_create(int device, wfsa_dev** out) {
         ctx->qw_poll_limit = 256;
     }
     if (const char* e = std::getenv("WFSA_QN_LAST_SELF")) ctx->qw_last_self = e[0] != '0';
+    if (const char* e = std::getenv("WFSA_QN_WAVE")) ctx->use_qn_wave = e[0] != '0';
     if (const char* e = std::getenv("WFSA_LL_DOT")) ctx->use_ll_dot = e[0] != '0';
     if (const char* e = std::getenv("WFSA_BUBBLE_SHAPES")) ctx->use_bubble_shapes = e[0] != '0';
 
@@ -3985,6 +4003,14 @@ static int qn_run_impl(wfsa_dev* ctx, double eta, double tol, int32_t max_steps,
                      int(ctx->comm != nullptr), int(ctx->qn_rmin), int(ctx->delta_on),
                      ctx->n_fall[0] + ctx->n_fall[1] + ctx->n_fall[2],
                      int(ctx->n_bubbles == 0 || bubbles_fused(ctx, false)), int(ctx->fixed_t_on), ctx->qn_k);
+    // qn_wave_kernel's limits, the in-kernel batches' admissibility test: every
+    // constraint 1 to kQnWaveMembers members and at most kQnWaveMaxChunks slot chunks
+    ctx->qnw_ok = ctx->qn_fused && ctx->qn_k > 0 && int64_t(ctx->h_cptr.size()) == int64_t(ctx->qn_k) + 1 &&
+                  ctx->lead_grp_nch <= wfsa::kQnWaveMaxChunks;
+    for (int32_t c = 0; ctx->qnw_ok && c < ctx->qn_k; ++c) {
+        const int32_t nm = ctx->h_cptr[size_t(c) + 1] - ctx->h_cptr[size_t(c)];
+        ctx->qnw_ok = nm >= 1 && nm <= wfsa::kQnWaveMembers;
+    }
     ctx->stats.qn_inkernel_waves = inkern ? ctx->qw_waves : 0;
     ctx->stats.qn_batches = inkern ? ctx->qw_nbatch : 0;
     if (inkern) {   // the second weight buffer

@@ -57,6 +57,7 @@ class DevStats(C.Structure):
         ("big_bubbles", i64), ("max_bubble_nodes", i32), ("max_bubble_edges", i32),
         ("generate_ms", dbl),
         ("dense_bp_tables_ms", dbl), ("dense_bp_forward_ms", dbl), ("dense_bp_backtrack_ms", dbl),
+        ("qn_wave_launches", i64),
     ]
 
 
