@@ -143,6 +143,9 @@ typedef struct {
      * kernel, the T forward steps, the back-track kernel */
     double dense_bp_tables_ms, dense_bp_forward_ms, dense_bp_backtrack_ms;
     int64_t qn_wave_launches;  /* QN steps so far whose update ran as qn_wave_kernel, a wave per constraint (WFSA_QN_WAVE=0: none; the others launch qn_step_kernel or ride in the stream kernel) */
+    /* last wfsa_dev_dense_sample_paths call (its sum is sample_path_ms): the
+     * forward pass (tables, the T steps, the final kernel), the backward kernel */
+    double dense_sp_forward_ms, dense_sp_backward_ms;
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -369,6 +372,82 @@ int wfsa_dev_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, uint64
                           double* logq /* [n_strings], NULL allowed */, int64_t* n_paths, int64_t* n_entries /* NULL allowed */);
 int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow /* [n_strings + 1] */, double* logw /* [n_paths] */,
                               int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
+/* Posterior path sampling on the dense path (stats.dense == 1), where no
+ * trellis is built and wfsa_dev_sample_paths fails: n independent draws per
+ * loaded string from P(path | string) at w_full, 1 <= n <= WFSA_SAMPLE_MAX, by
+ * forward filter / backward sample over the row slots of the dense path
+ * (dense_sample.hip).  Outputs as sample_paths gives them: logq[s] (-inf when
+ * the string has no accepting path of finite weight; NULL allowed), *n_paths,
+ * *n_entries (NULL allowed), and dense_sample_paths_get in kbest_paths_get's
+ * layout (any pointer may be NULL).  A string with an accepting path of finite
+ * weight owns exactly n paths, in sample-index order; every other string owns
+ * none.  Parameter ids follow dense_best_paths_get's conventions: path order,
+ * a transition before the emission it leads to, the end transition last,
+ * single-member groups without an id; an empty string with a finite ^ -> $
+ * edge has n copies of that edge as its paths.
+ *
+ * Forward.  The evaluation's own forward arithmetic at exp(w_full) (formed on
+ * the device as objective_grad forms it): dense_weights_kernel, the split-K
+ * RAW step GEMM and dense_fwd_epi_kernel per step, dense_final_kernel for
+ * log q -- this flow whatever WFSA_DENSE_ENGINE says -- into buffers of the
+ * sampler's own; the T x R x (np + pad) history of scaled alpha rows shares
+ * its allocation with dense_best_paths' score history (scratch of both).  On a
+ * context that runs the default engine logq equals objective_grad(w,
+ * want_logq)'s log q byte for byte.
+ *
+ * Backward.  For sample t of string s with L bytes, draw d = 0 chooses the end
+ * state among candidates of mass alpha_L[T] aend[T]; draw d = m (1 .. L - 1)
+ * the state at byte L - m among candidates of mass alpha_{L-m}[S] A[S][T], T
+ * the state chosen at byte L - m + 1; the ^ edge into byte 1 is one candidate
+ * and takes no draw.  A row's scale is common to its candidates and cancels.
+ * Draws are sample_paths' generator word for word (Philox4x32-10, key the
+ * seed, counter (lo32(s), hi32(s), t, d), u from words 0 and 1).
+ *
+ * A choice.  Candidates in ascending state order over the np padded states
+ * (padded states have mass 0), in groups of 64 consecutive states: a group's
+ * sum is a fixed butterfly over its 64 members, total the left-to-right sum
+ * of the group sums.  The group is the first whose running sum over the
+ * group sums exceeds u * total; the state is the first of that group whose
+ * running sum -- left to right over the members, from the running sum before
+ * the group -- exceeds u * total and exceeds the sum before it.  If rounding
+ * leaves none, the last member of positive mass (of the group; without a
+ * group, of all candidates).  Left-to-right sums of non-negative terms never
+ * decrease and a candidate is taken only where the sum grows, so a mass of 0
+ * (an absent edge, a -inf weight, a padded state, an alpha of 0) is never
+ * chosen.  If total == 0 (every product underflows) the lowest S with
+ * alpha[S] > 0 and A[S][T] > 0 is taken.  The association depends neither on
+ * n nor on the wave or lane that holds the sample: the same weights, n and
+ * seed give the same bytes on every call, and the first j samples of an n
+ * result are the j result byte for byte.
+ *
+ * logw[t] is the decoders' weight of the returned path, formed as
+ * dense_best_paths forms best_logw (an edge: the sum from 0.0 over its present
+ * parameters, transition then emission; the path: the sum from 0.0 over its
+ * edges, the end edge last) -- bit for bit what kbest_paths reports for that
+ * path under WFSA_DENSE=0; exp(logw[t] - logq[s]) is its posterior mass.
+ * Against sample_paths under WFSA_DENSE=0: the same uniforms and the same
+ * candidate order (in-edges by ascending source state, end nodes by ascending
+ * state for a model that qualifies for the dense path), the CDFs equal up to
+ * rounding (alpha * A here, exp(log alpha + lw - ...) there): a sample is the
+ * same path in both unless one of its choices falls closer to a CDF boundary
+ * than the two roundings differ.
+ *
+ * Needs a loaded model and corpus; no evaluation has to have run.  Local to
+ * the rank; leaves evaluations, rmin, the QN loop, generate and the
+ * dense_best_paths result untouched.  Valid until the next load or
+ * dense_sample_paths call.  stats.sample_path_ms = device time of its kernels
+ * (dense_sp_forward_ms + dense_sp_backward_ms).  WFSA_ERR_ARG when the model
+ * is not on the dense path (use wfsa_dev_sample_paths), before a model and a
+ * corpus are loaded, in matrix-file mode, while an evaluation is in flight,
+ * for n outside 1 .. WFSA_SAMPLE_MAX, for a w_full entry that is NaN or +inf
+ * (before any kernel runs), and from _get without a result since the last
+ * load; WFSA_ERR_CAPACITY, naming the bytes, when the history cannot be
+ * allocated or the fixed-size path output (2 n (total bytes + n_strings)
+ * int32) exceeds 4 GiB. */
+int wfsa_dev_dense_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, uint64_t seed,
+                                double* logq /* [n_strings], NULL ok */, int64_t* n_paths, int64_t* n_entries /* NULL ok */);
+int wfsa_dev_dense_sample_paths_get(wfsa_dev* ctx, int64_t* srow /* [n_strings + 1] */, double* logw /* [n_paths] */,
+                                    int64_t* prow /* [n_paths + 1] */, int32_t* pidx /* [n_entries] */);
 /* Test entry: the device's generator without an automaton, out[d] = the uniform
  * of draw d = 0 .. n_draws - 1 of sample `sample` of string `string` under
  * `seed` (the counter and key above). */

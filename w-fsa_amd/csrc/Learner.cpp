@@ -617,16 +617,23 @@ void Learner::SamplePaths(int32_t n, uint64_t seed, double* logq, int64_t* n_pat
     if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
     const double none = 0.0;
     get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
-    const int rc = wfsa_dev_sample_paths(dev, w_full.data(), n, seed, logq, n_paths, n_entries);
-    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_sample_paths: ", wfsa_dev_last_error());
-    ThrowOnDevError(rc, "wfsa_dev_sample_paths");
+    wfsa_dev_stats st;
+    ThrowOnDevError(wfsa_dev_get_stats(dev, &st), "wfsa_dev_get_stats");
+    sample_paths_dense = st.dense != 0;   // no trellis there: forward filter, backward sample over the row slots
+    const char* fn = sample_paths_dense ? "wfsa_dev_dense_sample_paths" : "wfsa_dev_sample_paths";
+    const int rc = sample_paths_dense ? wfsa_dev_dense_sample_paths(dev, w_full.data(), n, seed, logq, n_paths, n_entries)
+                                      : wfsa_dev_sample_paths(dev, w_full.data(), n, seed, logq, n_paths, n_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError(fn, ": ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, fn);
 }
 
 void Learner::SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const {
     if (!dev) throw LearnerUsageError("BuildFrom has not run");
-    const int rc = wfsa_dev_sample_paths_get(dev, srow, logw, prow, pidx);
-    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_sample_paths_get: ", wfsa_dev_last_error());
-    ThrowOnDevError(rc, "wfsa_dev_sample_paths_get");
+    const char* fn = sample_paths_dense ? "wfsa_dev_dense_sample_paths_get" : "wfsa_dev_sample_paths_get";
+    const int rc = sample_paths_dense ? wfsa_dev_dense_sample_paths_get(dev, srow, logw, prow, pidx)
+                                      : wfsa_dev_sample_paths_get(dev, srow, logw, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError(fn, ": ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, fn);
 }
 
 void Learner::Generate(int64_t n, int32_t max_len, uint64_t seed, int64_t* total_bytes, int64_t* n_entries, int64_t* status_counts) {

@@ -158,7 +158,8 @@ public:
     // GetWeight's w_full), 1 <= n <= WFSA_SAMPLE_MAX: n independent draws per
     // local recognized string; logq (nullable) = log q of each from the same
     // pass.  SamplePathsGet copies them out in KBestPathsGet's layout, a
-    // string's n paths in sample order
+    // string's n paths in sample order.  A model on the dense path is sampled
+    // by wfsa_dev_dense_sample_paths, same outputs
     void SamplePaths(int32_t n, uint64_t seed, double* logq, int64_t* n_paths, int64_t* n_entries);
     void SamplePathsGet(int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) const;
     // Unconditional generation at the current x (wfsa_dev_generate with
@@ -242,6 +243,7 @@ private:
     bool logq_valid = false;
     bool eval_in_flight = false, eval_logq = false;
     bool best_paths_dense = false;   // the last BestPaths ran the dense path's decoder
+    bool sample_paths_dense = false; // the last SamplePaths ran the dense path's sampler
 
     int device = 0;
     wfsa_dev* dev = nullptr;

@@ -304,7 +304,7 @@ hipError_t dalloc(T*& p, size_t n) {
 }  // namespace
 
 size_t DensePath::best_paths_history_bytes() const {
-    return size_t(T_) * size_t(R_) * size_t(np_) * sizeof(double);
+    return size_t(T_) * size_t(R_) * size_t(ldx_) * sizeof(double);
 }
 
 hipError_t DensePath::enqueue_best_paths(const double* w_full, hipEvent_t const ev[4], hipStream_t s) {
@@ -320,14 +320,7 @@ hipError_t DensePath::enqueue_best_paths(const double* w_full, hipEvent_t const 
         DTRY(dalloc(dcodes_, 2 * (size_t(total_sym_) + S)));
         DTRY(dalloc(dlogw_, S));
     }
-    if (!dhist_) {
-        const hipError_t e = dalloc(dhist_, size_t(T_) * R * np);
-        if (e != hipSuccess) {
-            dhist_ = nullptr;
-            (void)hipGetLastError();
-            return hipErrorOutOfMemory;
-        }
-    }
+    DTRY(history_alloc());   // (shared with the sampler's alpha rows: pitch np + pad there, np here)
     if (n_params_ > 0) DTRY(hipMemcpyAsync(dw_, w_full, size_t(n_params_) * sizeof(double), hipMemcpyHostToDevice, s));
     DTRY(hipEventRecord(ev[0], s));
     {

@@ -1219,6 +1219,10 @@ void DensePath::free_corpus() {
     dfree(lmat_); dfree(let_); dfree(l0_); dfree(lend_); dfree(mrow_); dfree(spart_); dfree(rpart_);
     dfree(doff_); dfree(dw_); dfree(dla_); dfree(dlat_); dfree(dle_); dfree(dl0_); dfree(dlend_); dfree(dhist_);
     dfree(dstates_); dfree(dcodes_); dfree(dlogw_);
+    dfree(fs_w_); dfree(fs_ewp_); dfree(fs_amat_); dfree(fs_amat_t_); dfree(fs_et_); dfree(fs_a0_); dfree(fs_aend_);
+    dfree(fs_la_); dfree(fs_sum_); dfree(fs_ysplit_); dfree(fs_logq_); dfree(fs_ll_);
+    dfree(fs_states_); dfree(fs_codes_); dfree(fs_logw_);
+    fs_n_ = 0;
     off_host_.clear();
     n_strings_ = 0;
     R_ = T_ = 0;
@@ -1683,6 +1687,77 @@ hipError_t DensePath::enqueue_lib(const double* w, const double* p, bool structu
         const int64_t n = int64_t(vocab_ + 2) * int64_t(np);
         dense_scatter_kernel<<<unsigned((n + 255) / 256), 256, 0, s>>>(c);
         DTRY(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+// The forward half of enqueue_lib's engine-2 flow, launch for launch, into
+// the caller's buffers (the sampler's: dense_sample.hip): the same kernels on
+// the same grids in the same order, so alpha, the scales and log q carry the
+// bits an evaluation at these weights computes.  No halted flag, no result
+// vector (n_out = 0), the ll partials into a buffer nobody reads.
+hipError_t DensePath::enqueue_forward_into(const double* ewp, const ForwardBufs& b, hipStream_t s) {
+    const size_t np = size_t(np_), R = size_t(R_);
+    {
+        WeightsArgs a{};
+        a.ewp = ewp;
+        a.code_a = code_a_; a.code_em = code_em_; a.code_s = code_s_; a.code_e = code_e_;
+        a.amat = b.amat; a.et = b.et; a.a0 = b.a0; a.aend = b.aend;
+        a.n_a = int64_t(np * np);
+        a.n_em = int64_t(size_t(vocab_ + 1) * np);
+        a.np = np_;
+        dense_weights_kernel<<<1024, 256, 0, s>>>(a);
+        DTRY(hipGetLastError());
+        dense_transpose_kernel<<<dim3(unsigned(np / 32), unsigned(np / 32)), 256, 0, s>>>(b.amat, b.amat_t, np_, nullptr);
+        DTRY(hipGetLastError());
+    }
+    if (n_strings_ == 0) return hipSuccess;
+    const size_t step = R * size_t(ldx_);
+    GemmArgs raw{};
+    raw.R = R_; raw.np = np_; raw.nct = nct_; raw.ldx = ldx_;
+    raw.out2 = b.ysplit; raw.splits = kSplitK;
+    const int raw_blocks = int((R / kT) * (np / kT)) * kSplitK;
+    EpiArgs g{};
+    g.np = np_; g.ldx = ldx_; g.et = b.et; g.a0 = b.a0; g.aend = b.aend;
+    for (int64_t t = -1; total_sym_ > 0 && t + 1 < T_; ++t) {
+        double* nxt = b.alpha + size_t(t + 1) * step;
+        if (t >= 0) {
+            GemmArgs m = raw;
+            m.x = b.alpha + size_t(t) * step;
+            m.bm = b.amat;
+            m.out = nxt;
+            if (step_cfg_ == 3) dense_gemm_kernel<RAW, kBkStep, 4><<<raw_blocks, 4 * 64, 0, s>>>(m);
+            else if (step_cfg_ >= 5) dense_gemm_kernel<RAW, kBkGrad, 8><<<raw_blocks, 8 * 64, 0, s>>>(m);
+            else dense_gemm_kernel<RAW, kBkGrad, kNwGrad><<<raw_blocks, kNwGrad * 64, 0, s>>>(m);
+            DTRY(hipGetLastError());
+        }
+        EpiArgs f = g;
+        f.io2 = t >= 0 ? b.ysplit : nullptr;
+        f.first = t < 0;
+        f.meta = meta_ + size_t(t + 1) * R;
+        f.sum_in = b.sum + size_t(t & 1) * R;
+        f.sum_out = b.sum + size_t((t + 1) & 1) * R;
+        f.io = nxt;
+        f.la_in = t < 0 ? b.la : b.la + size_t(t) * R;
+        f.la_out = b.la + size_t(t + 1) * R;
+        dense_fwd_epi_kernel<<<unsigned(R), kEpiThreads, 0, s>>>(f);
+        DTRY(hipGetLastError());
+    }
+    FinalArgs f{};
+    f.alpha = b.alpha; f.la = b.la; f.aend = b.aend; f.end_at = end_at_; f.p = p_; f.ewp = ewp;
+    f.code_se = code_se_; f.n_strings = n_strings_; f.np = np_; f.ldx = ldx_; f.logq = b.logq;
+    f.ll_part = b.ll_part;
+    dense_final_kernel<<<n_ll_, 256, 0, s>>>(f);
+    return hipGetLastError();
+}
+
+hipError_t DensePath::history_alloc() {
+    if (dhist_) return hipSuccess;
+    const hipError_t e = dalloc(dhist_, size_t(T_) * size_t(R_) * size_t(ldx_));
+    if (e != hipSuccess) {
+        dhist_ = nullptr;
+        (void)hipGetLastError();
+        return hipErrorOutOfMemory;
     }
     return hipSuccess;
 }

@@ -85,8 +85,9 @@ public:
     hipError_t enqueue_rmin(double* res, const unsigned* halted, hipStream_t s);
     // Viterbi decode at w_full (host, n_params log weights of which -inf is
     // the only non-finite value): a (max, +) pass over the same row slots
-    // that keeps every step's scores (T x R x np doubles, allocated by the
-    // first call since the load) and a back-track kernel that recomputes each
+    // that keeps every step's scores (T x R x np doubles in the history the
+    // sampler shares, allocated by the first call of either since the load
+    // at the evaluations' row pitch) and a back-track kernel that recomputes each
     // predecessor from them, ties to the lowest state (dense_decode.hip).
     // Buffers of its own: the evaluations' and the rmin pass's state is not
     // touched.  ev[0..3] are recorded before the table kernel, after it,
@@ -100,6 +101,27 @@ public:
     // last; an empty string has its ^ -> $ code alone
     hipError_t best_paths_download(double* logw, int32_t* codes, hipStream_t s) const;
     const std::vector<int64_t>& string_offsets() const { return off_host_; }
+    // Posterior path sampling at w_full (host, as for enqueue_best_paths):
+    // forward filter, backward sample (dense_sample.hip).  The forward pass is
+    // the evaluation's own -- dense_weights_kernel at exp(w_full), the split-K
+    // RAW step GEMM, dense_fwd_epi_kernel per step, dense_final_kernel for
+    // log q, whatever engine the evaluations run -- into buffers of the
+    // sampler's own, every step's scaled alpha row kept in the history the
+    // Viterbi decode keeps its scores in (scratch of both; no result outlives
+    // it).  Then one wavefront per (string, sample) walks back from the end:
+    // each state by inverse CDF over alpha[S] A[S][T] in ascending S with one
+    // Philox draw (sample.hpp), and forward again for the path's parameter
+    // codes and its weight as the decoders form it.  n samples per string,
+    // 1 .. kSampleMax.  ev[0..2] are recorded before the forward pass, after
+    // it and after the backward kernel.
+    // hipErrorOutOfMemory: the history (history_bytes) does not fit.
+    hipError_t enqueue_sample_paths(const double* w_full, int32_t n, uint64_t seed, hipEvent_t const ev[3], hipStream_t s);
+    // bytes of the fixed-size path output of n samples per string
+    size_t sample_paths_output_bytes(int32_t n) const;
+    // the last pass's results: logq[S], logw[S n] (-inf: no path) and
+    // codes[2 n (total_symbols + S)]: sample t of string s owns the pairs from
+    // 2 ((off[s] + s) n + t (L + 1)), laid out as best_paths_download's
+    hipError_t sample_paths_download(int32_t n, double* logq, double* logw, int32_t* codes, hipStream_t s) const;
 
     // the last evaluation ran at real weights (not the structural pass)
     bool weighted() const { return weighted_; }
@@ -197,6 +219,33 @@ private:
     int32_t* dstates_ = nullptr;  // [total symbols]
     int32_t* dcodes_ = nullptr;   // [2 (total symbols + S)]
     double* dlogw_ = nullptr;  // [S]
+    // Posterior sampling (allocated by its first call, freed with the corpus):
+    // the weights and exp of them, the forward pass's tables, scales and
+    // log q, the sampled states, codes and weights (fs_n_ samples per string)
+    double* fs_w_ = nullptr;       // [n_params]
+    double* fs_ewp_ = nullptr;     // [n_params]
+    double* fs_amat_ = nullptr;    // [np][np]
+    double* fs_amat_t_ = nullptr;  // [np][np] transposed
+    double* fs_et_ = nullptr;      // [vocab+1][np]
+    double* fs_a0_ = nullptr;      // [np]
+    double* fs_aend_ = nullptr;    // [np]
+    double* fs_la_ = nullptr;      // [T][R]
+    double* fs_sum_ = nullptr;     // [2][R]
+    double* fs_ysplit_ = nullptr;  // [R][ldx]
+    double* fs_logq_ = nullptr;    // [S]
+    double* fs_ll_ = nullptr;      // [blocks of dense_final_kernel]
+    int32_t* fs_states_ = nullptr; // [n total symbols]
+    int32_t* fs_codes_ = nullptr;  // [2 n (total symbols + S)]
+    double* fs_logw_ = nullptr;    // [S n]
+    int32_t fs_n_ = 0;
+    // the history both passes keep their rows in: [T][R][ldx] doubles
+    hipError_t history_alloc();
+    // the evaluation's forward pass (engine 2's flow) at ewp into the caller's
+    // buffers: the tables, alpha[T][R][ldx], la[T][R], log q
+    struct ForwardBufs {
+        double *amat, *amat_t, *et, *a0, *aend, *alpha, *la, *sum, *ysplit, *logq, *ll_part;
+    };
+    hipError_t enqueue_forward_into(const double* ewp, const ForwardBufs& b, hipStream_t s);
     hipError_t enqueue_lib(const double* w, const double* p, bool structural, double* out, double* logq,
                            const unsigned* halted, hipStream_t s);
     void free_corpus();

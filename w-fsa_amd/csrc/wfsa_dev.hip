@@ -500,6 +500,13 @@ struct wfsa_dev {
     std::vector<int64_t> dbp_prow;
     std::vector<int32_t> dbp_pidx;
     hipEvent_t dbp_ev[4] = {};
+    // the dense path's sampler (wfsa_dev_dense_sample_paths): its last result
+    // for _get, in kbest_paths_get's layout, and its three timing events
+    bool dsp_valid = false;
+    std::vector<int64_t> dsp_srow, dsp_prow;
+    std::vector<double> dsp_logw;
+    std::vector<int32_t> dsp_pidx;
+    hipEvent_t dsp_ev[3] = {};
     // Unconditional generation (wfsa_dev_generate; generate.hpp): the flattened
     // state graph as wfsa_model_desc gives it (uploaded with the model, on the
     // dense path too), the call's weights and running sums, the per-sample
@@ -3155,6 +3162,7 @@ void invalidate_decodes(wfsa_dev* ctx) {
     ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = ctx->pc.valid = ctx->bm.valid = false;
     ctx->gn_valid = false;
     ctx->dbp_valid = false;
+    ctx->dsp_valid = false;
     ctx->bm_base_ok = false;  // (the state sums' addresses belong to one model and one corpus)
 }
 
@@ -3354,6 +3362,8 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     for (hipEvent_t ev : ctx->gn_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->dbp_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : ctx->dsp_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
@@ -5082,6 +5092,89 @@ int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_
     if (logw && !ctx->sp_logw.empty()) std::memcpy(logw, ctx->sp_logw.data(), ctx->sp_logw.size() * sizeof(double));
     if (prow) std::memcpy(prow, ctx->sp_prow.data(), ctx->sp_prow.size() * sizeof(int64_t));
     if (pidx && !ctx->sp_pidx.empty()) std::memcpy(pidx, ctx->sp_pidx.data(), ctx->sp_pidx.size() * sizeof(int32_t));
+    return WFSA_OK;
+}
+
+// Posterior path sampling on the dense path: the evaluation's forward pass
+// into the sampler's buffers and the backward walk
+// (DensePath::enqueue_sample_paths), then the samples' parameter codes
+// filtered to Fsa parameter ids on the host
+int wfsa_dev_dense_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, uint64_t seed, double* logq, int64_t* n_paths,
+                                int64_t* n_entries) {
+    const char* name = "dense_sample_paths";
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to sample over", name);
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (n < 1 || n > WFSA_SAMPLE_MAX) return fail(WFSA_ERR_ARG, "%s: n = %d is outside 1 .. %d", name, int(n), WFSA_SAMPLE_MAX);
+    if (!ctx->dense)
+        return fail(WFSA_ERR_ARG, "%s: the model is not on the dense path; sample it with wfsa_dev_sample_paths", name);
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    for (int32_t j = 0; j < np; ++j)   // (-inf is the only non-finite value the pass may meet)
+        if (std::isnan(w_full[j]) || w_full[j] == INFINITY) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
+    const size_t out_bytes = ctx->dense->sample_paths_output_bytes(n);
+    if (out_bytes > (size_t(1) << 32))
+        return fail(WFSA_ERR_CAPACITY, "%s: the path output of %lld bytes (%d samples x %lld bytes and strings) exceeds 4 GiB", name,
+                    (long long)out_bytes, int(n), (long long)(ctx->dense->total_symbols() + ctx->n_strings));
+    ctx->dsp_valid = false;
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& ev : ctx->dsp_ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    const hipError_t e = ctx->dense->enqueue_sample_paths(w_full, n, seed, ctx->dsp_ev, s);
+    if (e == hipErrorOutOfMemory)
+        return fail(WFSA_ERR_CAPACITY, "%s: the alpha history of %lld bytes (%d steps x %d row slots x %d states) cannot be allocated", name,
+                    (long long)ctx->dense->best_paths_history_bytes(), ctx->dense->steps(), ctx->dense->rows(), ctx->dense->np());
+    HIP_TRY(e);
+    const int64_t S = ctx->n_strings;
+    const std::vector<int64_t>& off = ctx->dense->string_offsets();
+    std::vector<double> lq(size_t(S), 0.0), lw(size_t(S) * size_t(n), 0.0);
+    std::vector<int32_t> codes(2 * size_t(n) * size_t(off[size_t(S)] + S), wfsa::kCodeNone);
+    HIP_TRY(ctx->dense->sample_paths_download(n, lq.data(), lw.data(), codes.data(), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms[2] = {0.f, 0.f};
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ctx->dsp_ev[i], ctx->dsp_ev[i + 1]));
+    ctx->stats.dense_sp_forward_ms = double(ms[0]);
+    ctx->stats.dense_sp_backward_ms = double(ms[1]);
+    ctx->stats.sample_path_ms = double(ms[0]) + double(ms[1]);
+    ctx->dsp_srow.assign(size_t(S) + 1, 0);
+    ctx->dsp_prow.assign(1, 0);
+    ctx->dsp_logw.clear();
+    ctx->dsp_pidx.clear();
+    for (int64_t i = 0; i < S; ++i) {
+        const int64_t L = off[size_t(i) + 1] - off[size_t(i)];
+        if (lq[size_t(i)] > -INFINITY)
+            for (int32_t t = 0; t < n; ++t) {
+                const double v = lw[size_t(i) * size_t(n) + size_t(t)];
+                const int32_t* cd = codes.data() + 2 * ((off[size_t(i)] + i) * int64_t(n) + int64_t(t) * (L + 1));
+                if (cd[0] == wfsa::kCodeNone || !(v > -INFINITY))
+                    return fail(WFSA_ERR_HIP, "%s: string %lld, sample %d: the walk found no state of positive mass", name, (long long)i, int(t));
+                for (int64_t q = 0; q < 2 * (L + 1); ++q) {
+                    if (cd[q] == wfsa::kCodeNone || cd[q] >= np)
+                        return fail(WFSA_ERR_HIP, "%s: string %lld, sample %d: code %d at entry %lld is not a path edge", name, (long long)i,
+                                    int(t), int(cd[q]), (long long)q);
+                    if (cd[q] >= 0) ctx->dsp_pidx.push_back(cd[q]);
+                }
+                ctx->dsp_logw.push_back(v);
+                ctx->dsp_prow.push_back(int64_t(ctx->dsp_pidx.size()));
+            }
+        ctx->dsp_srow[size_t(i) + 1] = int64_t(ctx->dsp_logw.size());
+    }
+    ctx->dsp_valid = true;
+    if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
+    if (n_paths) *n_paths = int64_t(ctx->dsp_logw.size());
+    if (n_entries) *n_entries = int64_t(ctx->dsp_pidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_dense_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->dsp_valid)
+        return fail(WFSA_ERR_ARG, "dense_sample_paths_get: no wfsa_dev_dense_sample_paths result since the last load");
+    if (srow) std::memcpy(srow, ctx->dsp_srow.data(), ctx->dsp_srow.size() * sizeof(int64_t));
+    if (logw && !ctx->dsp_logw.empty()) std::memcpy(logw, ctx->dsp_logw.data(), ctx->dsp_logw.size() * sizeof(double));
+    if (prow) std::memcpy(prow, ctx->dsp_prow.data(), ctx->dsp_prow.size() * sizeof(int64_t));
+    if (pidx && !ctx->dsp_pidx.empty()) std::memcpy(pidx, ctx->dsp_pidx.data(), ctx->dsp_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
 

@@ -750,6 +750,24 @@ class Device:
         check_dev(load().wfsa_dev_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
         return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
 
+    def dense_sample_paths(self, w_full, n, seed=0):
+        """sample_paths for a model on the dense path (stats()["dense"] == 1),
+        where sample_paths has no trellis to walk: (srow, logw, prow, pidx,
+        logq) in sample_paths' layout, by forward filter / backward sample
+        over the dense row slots; logq carries objective_grad's bytes"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        n_paths, m = C.c_int64(), C.c_int64()
+        logq = np.zeros(self.n_strings, dtype=np.float64)
+        check_dev(load().wfsa_dev_dense_sample_paths(self._h, _ptr(w), int(n), int(seed), _ptr(logq), C.byref(n_paths), C.byref(m)))
+        srow = np.zeros(self.n_strings + 1, dtype=np.int64)
+        logw = np.zeros(max(n_paths.value, 1), dtype=np.float64)
+        prow = np.zeros(n_paths.value + 1, dtype=np.int64)
+        pidx = np.zeros(max(m.value, 1), dtype=np.int32)
+        check_dev(load().wfsa_dev_dense_sample_paths_get(self._h, _ptr(srow), _ptr(logw), _ptr(prow), _ptr(pidx)))
+        return srow, logw[:n_paths.value], prow, pidx[:m.value], logq
+
     def generate(self, w_full, n, max_len=255, seed=0):
         """n independent strings drawn from the loaded automaton itself at
         w_full (no corpus needed; works on the dense path): each state chooses

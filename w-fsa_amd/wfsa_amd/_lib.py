@@ -58,6 +58,7 @@ class DevStats(C.Structure):
         ("generate_ms", dbl),
         ("dense_bp_tables_ms", dbl), ("dense_bp_forward_ms", dbl), ("dense_bp_backtrack_ms", dbl),
         ("qn_wave_launches", i64),
+        ("dense_sp_forward_ms", dbl), ("dense_sp_backward_ms", dbl),
     ]
 
 
@@ -94,6 +95,8 @@ _SIGS = {
     "wfsa_dev_kbest_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_sample_paths": (C.c_int, [vp, vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
     "wfsa_dev_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
+    "wfsa_dev_dense_sample_paths": (C.c_int, [vp, vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
+    "wfsa_dev_dense_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_generate": (C.c_int, [vp, vp, i64, C.c_int32, C.c_uint64, P(i64), P(i64), vp]),
     "wfsa_dev_generate_get": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "wfsa_dev_posterior_counts": (C.c_int, [vp, vp, vp, vp, P(i64)]),
