@@ -146,6 +146,10 @@ typedef struct {
     /* last wfsa_dev_dense_sample_paths call (its sum is sample_path_ms): the
      * forward pass (tables, the T steps, the final kernel), the backward kernel */
     double dense_sp_forward_ms, dense_sp_backward_ms;
+    /* last wfsa_dev_dense_byte_marginals call (its sum is byte_marginal_ms): the
+     * forward pass, the backward pass, the count and fill kernels (0 with
+     * rows = 0), the tables, reward steps and back-track (0 with decode = 0) */
+    double dense_bm_forward_ms, dense_bm_backward_ms, dense_bm_rows_ms, dense_bm_decode_ms;
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */
@@ -590,6 +594,108 @@ int wfsa_dev_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t decode,
 int wfsa_dev_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow /* [total_symbols + 1] */, int32_t* midx /* [n_entries] */,
                                 double* mval /* [n_entries] */);
 int wfsa_dev_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow /* [n_strings + 1] */, int32_t* pidx /* [n_path_entries] */);
+
+/* Per-byte state posteriors and the MEA decode on the dense path (stats.dense
+ * == 1), where no trellis is built and wfsa_dev_byte_marginals fails
+ * (dense_marginals.hip).  On the dense path every interior state emits exactly
+ * one byte, so byte i of string s has one state on every path, and
+ *   mass[s, i, U] = P(the path is in Fsa state U at byte i | s),
+ * summing to 1 over U for every byte; the boundary after every byte is 1 and
+ * is not an output.  rows != 0 asks for the mass rows, decode != 0 for the MEA
+ * path of every string; at least one must be set.  rows = 0, decode = 1 is the
+ * decode alone: no row output, no 4 GiB rule.
+ * Outputs (every pointer may be NULL):
+ *   logq[s]       log q_s: dense_sample_paths' log q -- the evaluation's forward
+ *                 pass (DensePath::enqueue_forward_into, engine 2's flow whatever
+ *                 WFSA_DENSE_ENGINE says) into buffers of the call's own, the
+ *                 scaled alpha rows in the history dense_best_paths and
+ *                 dense_sample_paths share (scratch of all three).  On a context
+ *                 that runs the default engine it equals objective_grad(w,
+ *                 want_logq)'s log q byte for byte;
+ *   score[s], path_logw[s]  the MEA path's score and log weight (decode != 0
+ *                 only; untouched otherwise);
+ *   *n_entries    entries of all mass rows (0 with rows = 0); *n_path_entries
+ *                 the total length of the paths' parameter lists (0 without
+ *                 decode).
+ * dense_byte_marginals_get copies the rows out in byte_marginals_get's layout:
+ * corpus byte b = off[s] + i - 1 owns midx[mrow[b] .. mrow[b + 1]), Fsa state
+ * ids in wfsa_model_desc numbering, ascending, each with 0 < mval <= 1;
+ * WFSA_ERR_ARG when the last call had rows = 0.  dense_byte_marginals_path_get
+ * copies the MEA paths out in dense_best_paths_get's layout and conventions
+ * (pidx[prow[s] .. prow[s + 1]): Fsa parameter ids in path order, a transition
+ * before the emission it leads to, the end transition last, single-member
+ * groups without an id); WFSA_ERR_ARG when the last call had decode = 0.
+ *
+ * Masses.  Behind the forward pass the evaluation's own backward pass runs with
+ * p = 1 (DensePath::enqueue_backward_into: the split-K RAW GEMM against A^T and
+ * dense_bwd_epi_kernel per step, no gradient GEMM), so for the byte at step t
+ * of row slot r and interior state T
+ *   gamma = alpha_t[T] * beta_t[T] * exp(la_t + lb_t - log q_s)
+ * in the evaluation's scaled arithmetic, written over alpha in the history (the
+ * backward recursion never reads alpha).  The stored mass is min(gamma, 1.0); a
+ * state is listed when that value is > 0.  The interior states keep their order
+ * (the table from interior index to state id is built at model load), padded
+ * states and idle rows never appear.  Exactness for strings with one path is
+ * NOT promised, unlike byte_marginals': a mass of 1 comes out as the rounded
+ * product above, within 3e-11 * max(1, |log q_s|) * (L_s + 1) of 1.
+ * Rows.  One wavefront per corpus byte counts the byte's listed states (ballot
+ * and popcount over 64 states at a time), the host takes the prefix sum
+ * (mrow), and a second kernel writes every listed state at mrow[b] + the number
+ * of listed states below it: the rows do not depend on which wave took which
+ * byte.  More than 4 GiB of rows at 12 bytes an entry is refused with
+ * WFSA_ERR_CAPACITY and the byte count before the rows are allocated, and the
+ * call leaves no result; the caller slices the corpus, as for byte_marginals.
+ *
+ * MEA decode: the accepting path that maximises score = sum_i reward_i[state at
+ * byte i], reward the stored mass (the clamped double; 0.0 for an unlisted
+ * state).  Eligibility is read from the log tables dense_decode_tables_kernel
+ * writes (into tables of the call's own): an edge, emission, start or end is
+ * eligible when its entry is above -inf -- best_paths' notion of a finite
+ * weight, no exp involved.
+ *   D_1[T] = reward_1[T] where ^ -> T is eligible and T may emit byte 1;
+ *   D_j[T] = (max over S with S -> T eligible of D_{j-1}[S]) + reward_j[T]
+ *            where T may emit byte j; everything else is -inf.
+ * The max is taken first, then one add per byte: score is one left-to-right
+ * sum.  The pass is dense_best_paths' tile, T launches, every D_t kept -- over
+ * gamma in the history once the rows are out, so the decode needs no second
+ * history.  Back-track without back-pointers: the end state is the arg max of
+ * D_L over the states with an eligible end edge, each predecessor the arg max
+ * of D_{j-1}[S] over the S with S -> T eligible; ties go to the LOWEST state, a
+ * -inf candidate is never taken.  score[s] = D_L[end state]; path_logw[s] is
+ * the decoders' sum as dense_best_paths forms best_logw, bit for bit what
+ * kbest_paths reports for that path under WFSA_DENSE=0.  With rows = 0 the
+ * rewards are the same doubles, so paths, scores and weights are the bytes of
+ * a rows = 1 call.
+ * Ties against byte_marginals (WFSA_DENSE=0): there the order is source score,
+ * then log weight descending, then in-edge ascending; here source score, then
+ * lowest state.  At exact score ties the two tiers may return different paths
+ * of equal score.
+ *
+ * A string with log q = -inf owns nothing: empty rows, score NaN, path_logw
+ * -inf, empty path -- also where the log tables alone would find a route (exp
+ * underflow).  The empty string has no rows; with a finite ^ -> $ edge its path
+ * is that edge, its score 0.0 and its weight the edge's, as byte_marginals
+ * returns them.
+ *
+ * The rows, paths, scores and weights are copied out of the history during the
+ * call: a later dense_best_paths or dense_sample_paths call does not invalidate
+ * the result, and this call invalidates neither of theirs.  Evaluations, rmin,
+ * the QN loop, generate and captured graphs are untouched; local to the rank.
+ * Valid until the next load or dense_byte_marginals call.  stats.byte_marginal_ms
+ * = dense_bm_forward_ms + dense_bm_backward_ms + dense_bm_rows_ms +
+ * dense_bm_decode_ms.  WFSA_ERR_ARG when the model is not on the dense path
+ * (use wfsa_dev_byte_marginals), before a model and a corpus are loaded, in
+ * matrix-file mode, while an evaluation is in flight, for rows == 0 && decode
+ * == 0, for a w_full entry that is NaN or +inf (before any kernel runs), and
+ * from _get / _path_get without a result since the last load;
+ * WFSA_ERR_CAPACITY, naming the bytes, when the history or the rows cannot be
+ * allocated or the rows exceed 4 GiB. */
+int wfsa_dev_dense_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t rows, int32_t decode,
+                                  double* logq /* [n_strings] */, double* score /* [n_strings] */,
+                                  double* path_logw /* [n_strings] */, int64_t* n_entries, int64_t* n_path_entries);
+int wfsa_dev_dense_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow /* [total_symbols + 1] */, int32_t* midx /* [n_entries] */,
+                                      double* mval /* [n_entries] */);
+int wfsa_dev_dense_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow /* [n_strings + 1] */, int32_t* pidx /* [n_path_entries] */);
 
 /* Unconditional generation: n independent strings drawn from the automaton
  * itself at w_full, each with its path and weights.  The call needs a loaded

@@ -176,7 +176,10 @@ int wfsa_learner_posterior_counts_get(wfsa_learner* l, int64_t* crow /* [n_local
  * midx[mrow[b] .. mrow[b + 1]) (wfsa_fsa_state_name gives their names),
  * ascending, mval > 0.  byte_marginals_path_get copies the MEA paths out in
  * best_paths_get's layout; it fails after a call with decode = 0.  Local to the
- * rank: no collective. */
+ * rank: no collective.  A model on the dense path is served by
+ * wfsa_dev_dense_byte_marginals (rows = 1): the same outputs, boundary 1.0
+ * after every byte (NaN on the bytes of a string with logq -inf), MEA ties to
+ * the lowest state. */
 int wfsa_learner_byte_marginals(wfsa_learner* l, int32_t decode, double* logq /* [n_local_strings] */,
                                 double* boundary /* [n_local_bytes] */, double* score /* [n_local_strings] */,
                                 double* path_logw /* [n_local_strings] */, int64_t* n_entries, int64_t* n_path_entries);

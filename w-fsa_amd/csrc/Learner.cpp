@@ -676,23 +676,44 @@ void Learner::ByteMarginals(bool decode, double* logq, double* boundary, double*
     if (eval_in_flight) throw LearnerUsageError("an evaluation is in flight");
     const double none = 0.0;
     get_weights(n_full, trimmed_weights.data(), _x.empty() ? &none : _x.data(), w_full.data());
-    const int rc = wfsa_dev_byte_marginals(dev, w_full.data(), decode ? 1 : 0, logq, boundary, score, path_logw, n_entries, n_path_entries);
-    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_byte_marginals: ", wfsa_dev_last_error());
-    ThrowOnDevError(rc, "wfsa_dev_byte_marginals");
+    wfsa_dev_stats st;
+    ThrowOnDevError(wfsa_dev_get_stats(dev, &st), "wfsa_dev_get_stats");
+    byte_marginals_dense = st.dense != 0;   // no trellis there: the evaluation's forward and backward passes over the row slots
+    if (!byte_marginals_dense) {
+        const int rc = wfsa_dev_byte_marginals(dev, w_full.data(), decode ? 1 : 0, logq, boundary, score, path_logw, n_entries, n_path_entries);
+        if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_byte_marginals: ", wfsa_dev_last_error());
+        ThrowOnDevError(rc, "wfsa_dev_byte_marginals");
+        return;
+    }
+    // every interior state of a dense model emits one byte: the boundary after a byte is 1 (NaN where the string has no path)
+    std::vector<double> lq(size_t(st.n_strings), 0.0);
+    const int rc = wfsa_dev_dense_byte_marginals(dev, w_full.data(), 1, decode ? 1 : 0, lq.data(), score, path_logw, n_entries, n_path_entries);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_dense_byte_marginals: ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, "wfsa_dev_dense_byte_marginals");
+    if (logq && !lq.empty()) std::memcpy(logq, lq.data(), lq.size() * sizeof(double));
+    if (boundary) {
+        std::vector<int64_t> mrow(size_t(st.total_symbols) + 1, 0);
+        ThrowOnDevError(wfsa_dev_dense_byte_marginals_get(dev, mrow.data(), nullptr, nullptr), "wfsa_dev_dense_byte_marginals_get");
+        // a byte's masses sum to 1, so its row is empty exactly when its string has log q = -inf
+        for (int64_t b = 0; b < st.total_symbols; ++b)
+            boundary[b] = mrow[size_t(b) + 1] > mrow[size_t(b)] ? 1.0 : std::numeric_limits<double>::quiet_NaN();
+    }
 }
 
 void Learner::ByteMarginalsGet(int64_t* mrow, int32_t* midx, double* mval) const {
     if (!dev) throw LearnerUsageError("BuildFrom has not run");
-    const int rc = wfsa_dev_byte_marginals_get(dev, mrow, midx, mval);
-    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_byte_marginals_get: ", wfsa_dev_last_error());
-    ThrowOnDevError(rc, "wfsa_dev_byte_marginals_get");
+    const char* fn = byte_marginals_dense ? "wfsa_dev_dense_byte_marginals_get" : "wfsa_dev_byte_marginals_get";
+    const int rc = byte_marginals_dense ? wfsa_dev_dense_byte_marginals_get(dev, mrow, midx, mval) : wfsa_dev_byte_marginals_get(dev, mrow, midx, mval);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError(fn, ": ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, fn);
 }
 
 void Learner::ByteMarginalsPathGet(int64_t* prow, int32_t* pidx) const {
     if (!dev) throw LearnerUsageError("BuildFrom has not run");
-    const int rc = wfsa_dev_byte_marginals_path_get(dev, prow, pidx);
-    if (rc == WFSA_ERR_ARG) throw LearnerUsageError("wfsa_dev_byte_marginals_path_get: ", wfsa_dev_last_error());
-    ThrowOnDevError(rc, "wfsa_dev_byte_marginals_path_get");
+    const char* fn = byte_marginals_dense ? "wfsa_dev_dense_byte_marginals_path_get" : "wfsa_dev_byte_marginals_path_get";
+    const int rc = byte_marginals_dense ? wfsa_dev_dense_byte_marginals_path_get(dev, prow, pidx) : wfsa_dev_byte_marginals_path_get(dev, prow, pidx);
+    if (rc == WFSA_ERR_ARG) throw LearnerUsageError(fn, ": ", wfsa_dev_last_error());
+    ThrowOnDevError(rc, fn);
 }
 
 }  // namespace wfsa

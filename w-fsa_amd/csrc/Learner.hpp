@@ -182,7 +182,10 @@ public:
     // decode, the MEA path's score and log weight per string (every pointer
     // nullable).  ByteMarginalsGet copies the mass rows out: byte b owns the
     // state ids midx[mrow[b] .. mrow[b + 1]), ascending, mval > 0;
-    // ByteMarginalsPathGet the MEA paths in BestPathsGet's layout
+    // ByteMarginalsPathGet the MEA paths in BestPathsGet's layout.  A model on
+    // the dense path is served by wfsa_dev_dense_byte_marginals (rows = 1),
+    // same outputs; its boundary is 1.0 after every byte (NaN on the bytes of
+    // a string without a path)
     void ByteMarginals(bool decode, double* logq, double* boundary, double* score, double* path_logw, int64_t* n_entries,
                        int64_t* n_path_entries);
     void ByteMarginalsGet(int64_t* mrow, int32_t* midx, double* mval) const;
@@ -244,6 +247,7 @@ private:
     bool eval_in_flight = false, eval_logq = false;
     bool best_paths_dense = false;   // the last BestPaths ran the dense path's decoder
     bool sample_paths_dense = false; // the last SamplePaths ran the dense path's sampler
+    bool byte_marginals_dense = false; // the last ByteMarginals ran the dense path's passes
 
     int device = 0;
     wfsa_dev* dev = nullptr;

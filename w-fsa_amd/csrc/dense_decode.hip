@@ -307,6 +307,21 @@ size_t DensePath::best_paths_history_bytes() const {
     return size_t(T_) * size_t(R_) * size_t(ldx_) * sizeof(double);
 }
 
+// the log tables at w (device) into the caller's buffers (the MEA decode reads
+// its eligibility from tables of its own: dense_marginals.hip)
+hipError_t DensePath::enqueue_decode_tables_into(const double* w, const DecodeTables& t, hipStream_t s) {
+    const size_t np = size_t(np_);
+    DecodeTableArgs a{};
+    a.w = w;
+    a.code_a = code_a_; a.code_em = code_em_; a.code_s = code_s_; a.code_e = code_e_;
+    a.la = t.la; a.lat = t.lat; a.le = t.le; a.l0 = t.l0; a.lend = t.lend;
+    a.n_em = int64_t(size_t(vocab_ + 1) * np);
+    a.np = np_;
+    const dim3 grid(unsigned(np / 32), unsigned(np / 32));
+    dense_decode_tables_kernel<<<grid, 256, 0, s>>>(a);
+    return hipGetLastError();
+}
+
 hipError_t DensePath::enqueue_best_paths(const double* w_full, hipEvent_t const ev[4], hipStream_t s) {
     const size_t np = size_t(np_), R = size_t(R_), S = size_t(n_strings_);
     if (!dla_) {   // first call since the load: the pass's buffers
@@ -323,17 +338,7 @@ hipError_t DensePath::enqueue_best_paths(const double* w_full, hipEvent_t const 
     DTRY(history_alloc());   // (shared with the sampler's alpha rows: pitch np + pad there, np here)
     if (n_params_ > 0) DTRY(hipMemcpyAsync(dw_, w_full, size_t(n_params_) * sizeof(double), hipMemcpyHostToDevice, s));
     DTRY(hipEventRecord(ev[0], s));
-    {
-        DecodeTableArgs a{};
-        a.w = dw_;
-        a.code_a = code_a_; a.code_em = code_em_; a.code_s = code_s_; a.code_e = code_e_;
-        a.la = dla_; a.lat = dlat_; a.le = dle_; a.l0 = dl0_; a.lend = dlend_;
-        a.n_em = int64_t(size_t(vocab_ + 1) * np);
-        a.np = np_;
-        const dim3 grid(unsigned(np / 32), unsigned(np / 32));
-        dense_decode_tables_kernel<<<grid, 256, 0, s>>>(a);
-        DTRY(hipGetLastError());
-    }
+    DTRY(enqueue_decode_tables_into(dw_, DecodeTables{dla_, dlat_, dle_, dl0_, dlend_}, s));
     DTRY(hipEventRecord(ev[1], s));
     if (total_sym_ > 0) {
         MaxPlusArgs g{};

@@ -1160,6 +1160,9 @@ std::string dense_model_build(const wfsa_model_desc& d, bool force, DenseModel& 
     m.np = (n_int + kDenseTile - 1) / kDenseTile * kDenseTile;
     m.n_params = d.n_params;
     m.n_transitions = n_tr;
+    m.state_id.resize(size_t(n_int));
+    for (int32_t s = 0; s < N; ++s)
+        if (idx[size_t(s)] >= 0) m.state_id[size_t(idx[size_t(s)])] = s;
     int32_t V = 0;
     for (int b = 0; b < 256; ++b) m.sym_of_byte[b] = -1;
     for (int b = 0; b < 256; ++b)
@@ -1206,7 +1209,7 @@ DensePath::~DensePath() {
 }
 
 void DensePath::free_model() {
-    dfree(code_a_); dfree(code_s_); dfree(code_e_); dfree(code_em_);
+    dfree(code_a_); dfree(code_s_); dfree(code_e_); dfree(code_em_); dfree(state_id_);
     dfree(amat_); dfree(amat_t_); dfree(et_); dfree(a0_); dfree(aend_); dfree(ones_); dfree(gbuf_);
     if (blas_) (void)rocblas_destroy_handle(static_cast<rocblas_handle>(blas_));
     blas_ = nullptr;
@@ -1223,6 +1226,12 @@ void DensePath::free_corpus() {
     dfree(fs_la_); dfree(fs_sum_); dfree(fs_ysplit_); dfree(fs_logq_); dfree(fs_ll_);
     dfree(fs_states_); dfree(fs_codes_); dfree(fs_logw_);
     fs_n_ = 0;
+    dfree(bm_.w); dfree(bm_.ewp); dfree(bm_.amat); dfree(bm_.amat_t); dfree(bm_.et); dfree(bm_.a0); dfree(bm_.aend);
+    dfree(bm_.la); dfree(bm_.lb); dfree(bm_.sum); dfree(bm_.y); dfree(bm_.ysplit); dfree(bm_.z); dfree(bm_.logq); dfree(bm_.ll);
+    dfree(bm_.rowof); dfree(bm_.cnt); dfree(bm_.mrow); dfree(bm_.midx); dfree(bm_.mval);
+    dfree(bm_.tla); dfree(bm_.tlat); dfree(bm_.tle); dfree(bm_.tl0); dfree(bm_.tlend);
+    dfree(bm_.states); dfree(bm_.codes); dfree(bm_.logw); dfree(bm_.score);
+    bm_mrow_host_.clear();
     off_host_.clear();
     n_strings_ = 0;
     R_ = T_ = 0;
@@ -1238,6 +1247,7 @@ hipError_t DensePath::load_model(const DenseModel& m, hipStream_t s) {
     free_model();
     n_params_ = m.n_params;
     np_ = m.np;
+    n_states_ = m.n_states;
     vocab_ = m.vocab;
     nct_ = m.np / kT;
     code_se_ = m.code_se;
@@ -1251,6 +1261,8 @@ hipError_t DensePath::load_model(const DenseModel& m, hipStream_t s) {
     DTRY(hipMemcpyAsync(code_s_, m.code_s.data(), np * 4, hipMemcpyHostToDevice, s));
     DTRY(hipMemcpyAsync(code_e_, m.code_e.data(), np * 4, hipMemcpyHostToDevice, s));
     DTRY(hipMemcpyAsync(code_em_, m.code_em.data(), size_t(vocab_ + 1) * np * 4, hipMemcpyHostToDevice, s));
+    DTRY(dalloc(state_id_, size_t(n_states_)));
+    DTRY(hipMemcpyAsync(state_id_, m.state_id.data(), size_t(n_states_) * 4, hipMemcpyHostToDevice, s));
     DTRY(dalloc(amat_, np * np));
     DTRY(dalloc(amat_t_, np * np));
     DTRY(dalloc(et_, size_t(vocab_ + 1) * np));
@@ -1749,6 +1761,54 @@ hipError_t DensePath::enqueue_forward_into(const double* ewp, const ForwardBufs&
     f.ll_part = b.ll_part;
     dense_final_kernel<<<n_ll_, 256, 0, s>>>(f);
     return hipGetLastError();
+}
+
+// The backward half of enqueue_lib's engine-2 flow, launch for launch, into
+// the caller's buffers (the byte marginals': dense_marginals.hip), with p = 1
+// and without the gradient: the split-K RAW GEMM against A^T and
+// dense_bwd_epi_kernel per step, T - 1 down to 0.  la_prev is not passed, so
+// f2 = 0 and z -- one block every step overwrites -- holds zeros.
+hipError_t DensePath::enqueue_backward_into(const BackwardBufs& b, hipStream_t s) {
+    const size_t np = size_t(np_), R = size_t(R_);
+    if (n_strings_ == 0 || total_sym_ == 0) return hipSuccess;
+    const size_t step = R * size_t(ldx_);
+    GemmArgs raw{};
+    raw.R = R_; raw.np = np_; raw.nct = nct_; raw.ldx = ldx_;
+    raw.out2 = b.ysplit; raw.splits = kSplitK;
+    const int raw_blocks = int((R / kT) * (np / kT)) * kSplitK;
+    EpiArgs g{};
+    g.np = np_; g.ldx = ldx_; g.et = b.et; g.aend = b.aend; g.p = pones_; g.logq = b.logq;
+    for (int64_t t = T_ - 1; t >= 0; --t) {
+        double* cur = b.y + size_t(t & 1) * step;
+        if (t < T_ - 1) {
+            GemmArgs m = raw;
+            m.x = b.y + size_t((t + 1) & 1) * step;
+            m.bm = b.amat_t;
+            m.out = cur;
+            if (step_cfg_ == 3) dense_gemm_kernel<RAW, kBkStep, 4><<<raw_blocks, 4 * 64, 0, s>>>(m);
+            else if (step_cfg_ >= 5) dense_gemm_kernel<RAW, kBkGrad, 8><<<raw_blocks, 8 * 64, 0, s>>>(m);
+            else dense_gemm_kernel<RAW, kBkGrad, kNwGrad><<<raw_blocks, kNwGrad * 64, 0, s>>>(m);
+            DTRY(hipGetLastError());
+        }
+        EpiArgs e = g;
+        e.io2 = t < T_ - 1 ? b.ysplit : nullptr;
+        e.first = t == T_ - 1;
+        e.meta = meta_ + size_t(t) * R;
+        e.sid = sid_ + size_t(t) * R;
+        e.sum_in = b.sum + size_t((t + 1) & 1) * R;
+        e.sum_out = b.sum + size_t(t & 1) * R;
+        e.io = cur;
+        e.lb_in = b.lb + size_t(std::min<int64_t>(t + 1, T_ - 1)) * R;
+        e.lb_out = b.lb + size_t(t) * R;
+        e.la_t = b.la + size_t(t) * R;
+        e.la_prev = nullptr;
+        e.alpha_t = b.alpha + size_t(t) * step;
+        e.gam = b.gam + size_t(t) * step;
+        e.z = b.z;
+        dense_bwd_epi_kernel<<<unsigned(R), kEpiThreads, 0, s>>>(e);
+        DTRY(hipGetLastError());
+    }
+    return hipSuccess;
 }
 
 hipError_t DensePath::history_alloc() {

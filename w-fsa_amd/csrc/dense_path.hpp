@@ -49,6 +49,7 @@ struct DenseModel {
     std::vector<int32_t> code_em;  // [vocab+1][np] T emits symbol v (row vocab: none)
     int32_t code_se = kCodeNone;   // ^->$ (the empty string)
     int64_t n_transitions = 0;     // interior S->T edges
+    std::vector<int32_t> state_id; // [n_states] interior index -> Fsa state id (wfsa_model_desc numbering), ascending
 };
 
 // Builds the dense tables when the automaton qualifies: every state other
@@ -122,6 +123,40 @@ public:
     // codes[2 n (total_symbols + S)]: sample t of string s owns the pairs from
     // 2 ((off[s] + s) n + t (L + 1)), laid out as best_paths_download's
     hipError_t sample_paths_download(int32_t n, double* logq, double* logw, int32_t* codes, hipStream_t s) const;
+    // Per-byte state posteriors and the MEA decode at w_full (host, as for
+    // enqueue_best_paths; dense_marginals.hip), in four phases on one stream,
+    // buffers of the feature's own except the shared history:
+    //   byte_marginals_masses  the evaluation's forward pass (as the sampler
+    //                          runs it) and its backward pass with p = 1
+    //                          (enqueue_backward_into), gamma written over
+    //                          alpha in the history: the history then holds
+    //                          alpha beta exp(la + lb - log q) per slot and state
+    //   byte_marginals_count   a wavefront per corpus byte counts the interior
+    //                          states with min(gamma, 1) > 0; the prefix sum
+    //                          is taken on the host (synchronises); returns
+    //                          the number of entries
+    //   byte_marginals_fill    allocates the rows and fills them: Fsa state
+    //                          ids ascending, the clamped masses
+    //   byte_marginals_decode  dense_decode_tables_kernel into tables of its
+    //                          own, lA turned into a 0 / -inf mask, T reward
+    //                          (max, +) steps that write D over gamma in the
+    //                          history, and the back-track
+    // ev[0..7]: before / after the forward pass, after the backward pass,
+    // after the count, before / after the fill, before / after the decode.
+    // hipErrorOutOfMemory from _masses: the history does not fit; from _fill:
+    // the rows do not.
+    hipError_t byte_marginals_masses(const double* w_full, hipEvent_t const ev[8], hipStream_t s);
+    hipError_t byte_marginals_count(int64_t* n_entries, hipEvent_t const ev[8], hipStream_t s);
+    hipError_t byte_marginals_fill(hipEvent_t const ev[8], hipStream_t s);
+    hipError_t byte_marginals_decode(hipEvent_t const ev[8], hipStream_t s);
+    // results: logq[S]; the rows (mrow[total_symbols + 1] from the count,
+    // midx / mval of its last entry's length); score[S] (NaN: no path),
+    // logw[S] and codes as best_paths_download gives them
+    hipError_t byte_marginals_logq_download(double* logq, hipStream_t s) const;
+    const std::vector<int64_t>& byte_marginals_mrow() const { return bm_mrow_host_; }
+    hipError_t byte_marginals_rows_download(int32_t* midx, double* mval, hipStream_t s) const;
+    void byte_marginals_rows_release();   // (the rows live on the host after the download)
+    hipError_t byte_marginals_paths_download(double* score, double* logw, int32_t* codes, hipStream_t s) const;
 
     // the last evaluation ran at real weights (not the structural pass)
     bool weighted() const { return weighted_; }
@@ -149,6 +184,7 @@ private:
     // 4-wave blocks, 2 K slices of 16, 3 engine 2 with K slices of 32, 4 engine 3 with its own gradient GEMM
     int step_cfg_ = 5;
     int32_t n_params_ = 0, np_ = 0, vocab_ = 0, nct_ = 0;
+    int32_t n_states_ = 0;             // interior states (np_ without the padding)
     int32_t code_se_ = kCodeNone;
     int16_t sym_of_byte_[256] = {};
     int64_t n_strings_ = 0, total_sym_ = 0;
@@ -162,6 +198,7 @@ private:
     int32_t* code_s_ = nullptr;
     int32_t* code_e_ = nullptr;
     int32_t* code_em_ = nullptr;
+    int32_t* state_id_ = nullptr;  // [n_states] interior index -> Fsa state id
     // per-iteration weights
     double* amat_ = nullptr;   // [np][np]
     double* amat_t_ = nullptr; // [np][np] transposed
@@ -246,6 +283,41 @@ private:
         double *amat, *amat_t, *et, *a0, *aend, *alpha, *la, *sum, *ysplit, *logq, *ll_part;
     };
     hipError_t enqueue_forward_into(const double* ewp, const ForwardBufs& b, hipStream_t s);
+    // the evaluation's backward pass (engine 2's flow) with p = 1 behind a
+    // forward pass into the same buffers: gam[T][R][ldx] = alpha beta
+    // exp(la + lb - log q) (gam may be alpha: a step reads and writes its own
+    // elements alone, and the recursion never reads alpha), lb[T][R]; y is
+    // [2][R][ldx], z one [R][ldx] block every step overwrites (the gradient
+    // GEMM that would read it does not run)
+    struct BackwardBufs {
+        const double *amat_t, *et, *aend, *alpha, *la, *logq;
+        double *gam, *lb, *sum, *y, *ysplit, *z;
+    };
+    hipError_t enqueue_backward_into(const BackwardBufs& b, hipStream_t s);
+    // dense_decode_tables_kernel at w (device) into the caller's log tables
+    struct DecodeTables {
+        double *la, *lat, *le, *l0, *lend;
+    };
+    hipError_t enqueue_decode_tables_into(const double* w, const DecodeTables& t, hipStream_t s);
+    // Byte marginals and the MEA decode (allocated by its first call, freed
+    // with the corpus): the forward and backward passes' tables and scales,
+    // the row of every corpus byte, the rows, the decode's tables and paths
+    struct ByteMarginalBufs {
+        double *w = nullptr, *ewp = nullptr;                                          // [n_params]
+        double *amat = nullptr, *amat_t = nullptr;                                    // [np][np]
+        double *et = nullptr, *a0 = nullptr, *aend = nullptr;                         // [vocab+1][np], [np], [np]
+        double *la = nullptr, *lb = nullptr, *sum = nullptr;                          // [T][R], [T][R], [2][R]
+        double *y = nullptr, *ysplit = nullptr, *z = nullptr;                         // [2][R][ldx], [R][ldx], [R][ldx]
+        double *logq = nullptr, *ll = nullptr;                                        // [S], [blocks of dense_final_kernel]
+        int32_t *rowof = nullptr, *cnt = nullptr;                                     // [total symbols]: t R + r of the byte; its entries
+        int64_t* mrow = nullptr;                                                      // [total symbols + 1]
+        int32_t* midx = nullptr;                                                      // [entries]
+        double* mval = nullptr;                                                       // [entries]
+        double *tla = nullptr, *tlat = nullptr, *tle = nullptr, *tl0 = nullptr, *tlend = nullptr;   // the decode's tables
+        int32_t *states = nullptr, *codes = nullptr;                                  // [total symbols], [2 (total symbols + S)]
+        double *logw = nullptr, *score = nullptr;                                     // [S]
+    } bm_;
+    std::vector<int64_t> bm_mrow_host_;   // [total symbols + 1] the last count's prefix sum
     hipError_t enqueue_lib(const double* w, const double* p, bool structural, double* out, double* logq,
                            const unsigned* halted, hipStream_t s);
     void free_corpus();

@@ -507,6 +507,14 @@ struct wfsa_dev {
     std::vector<double> dsp_logw;
     std::vector<int32_t> dsp_pidx;
     hipEvent_t dsp_ev[3] = {};
+    // the dense path's byte marginals and MEA decode
+    // (wfsa_dev_dense_byte_marginals): its last result for _get / _path_get
+    // in byte_marginals' layouts, and its eight timing events
+    bool dbm_valid = false, dbm_has_rows = false, dbm_has_path = false;
+    std::vector<int64_t> dbm_mrow, dbm_prow;
+    std::vector<int32_t> dbm_midx, dbm_pidx;
+    std::vector<double> dbm_mval;
+    hipEvent_t dbm_ev[8] = {};
     // Unconditional generation (wfsa_dev_generate; generate.hpp): the flattened
     // state graph as wfsa_model_desc gives it (uploaded with the model, on the
     // dense path too), the call's weights and running sums, the per-sample
@@ -3163,6 +3171,7 @@ void invalidate_decodes(wfsa_dev* ctx) {
     ctx->gn_valid = false;
     ctx->dbp_valid = false;
     ctx->dsp_valid = false;
+    ctx->dbm_valid = false;
     ctx->bm_base_ok = false;  // (the state sums' addresses belong to one model and one corpus)
 }
 
@@ -3364,6 +3373,8 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     for (hipEvent_t ev : ctx->dbp_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ctx->dsp_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : ctx->dbm_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
@@ -5175,6 +5186,137 @@ int wfsa_dev_dense_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, 
     if (logw && !ctx->dsp_logw.empty()) std::memcpy(logw, ctx->dsp_logw.data(), ctx->dsp_logw.size() * sizeof(double));
     if (prow) std::memcpy(prow, ctx->dsp_prow.data(), ctx->dsp_prow.size() * sizeof(int64_t));
     if (pidx && !ctx->dsp_pidx.empty()) std::memcpy(pidx, ctx->dsp_pidx.data(), ctx->dsp_pidx.size() * sizeof(int32_t));
+    return WFSA_OK;
+}
+
+// Byte marginals and the MEA decode on the dense path: the evaluation's forward
+// and backward passes into the feature's buffers, the rows out of the slots,
+// the reward (max, +) pass and its back-track (DensePath::byte_marginals_*),
+// then the paths' parameter codes filtered to Fsa parameter ids on the host
+int wfsa_dev_dense_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t rows, int32_t decode, double* logq, double* score,
+                                  double* path_logw, int64_t* n_entries, int64_t* n_path_entries) {
+    const char* name = "dense_byte_marginals";
+    if (int rc = check_ctx(ctx)) return rc;
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to walk", name);
+    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
+    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (!rows && !decode) return fail(WFSA_ERR_ARG, "%s: rows = 0 and decode = 0 ask for nothing", name);
+    if (!ctx->dense)
+        return fail(WFSA_ERR_ARG, "%s: the model is not on the dense path; take its marginals with wfsa_dev_byte_marginals", name);
+    const int32_t np = ctx->n_params;
+    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    for (int32_t j = 0; j < np; ++j)   // (-inf is the only non-finite value the pass may meet)
+        if (std::isnan(w_full[j]) || w_full[j] == INFINITY) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
+    ctx->dbm_valid = false;
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& ev : ctx->dbm_ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    wfsa::DensePath& dp = *ctx->dense;
+    hipError_t e = dp.byte_marginals_masses(w_full, ctx->dbm_ev, s);
+    if (e == hipErrorOutOfMemory)
+        return fail(WFSA_ERR_CAPACITY, "%s: the history of %lld bytes (%d steps x %d row slots x %d states) cannot be allocated", name,
+                    (long long)dp.best_paths_history_bytes(), dp.steps(), dp.rows(), dp.np());
+    HIP_TRY(e);
+    const int64_t S = ctx->n_strings, B = dp.total_symbols();
+    int64_t entries = 0;
+    if (rows) {
+        HIP_TRY(dp.byte_marginals_count(&entries, ctx->dbm_ev, s));
+        constexpr int64_t kRowBudget = int64_t(4) << 30;
+        if (entries * 12 > kRowBudget)
+            return fail(WFSA_ERR_CAPACITY, "%s: the mass rows take %lld bytes (%lld entries of 12 bytes over %lld corpus bytes), over 4 GiB", name,
+                        (long long)(entries * 12), (long long)entries, (long long)B);
+        e = dp.byte_marginals_fill(ctx->dbm_ev, s);
+        if (e == hipErrorOutOfMemory)
+            return fail(WFSA_ERR_CAPACITY, "%s: the mass rows of %lld bytes cannot be allocated", name, (long long)(entries * 12));
+        HIP_TRY(e);
+    }
+    if (decode) HIP_TRY(dp.byte_marginals_decode(ctx->dbm_ev, s));
+    const std::vector<int64_t>& off = dp.string_offsets();
+    std::vector<double> lq(size_t(S), 0.0), sc, plw;
+    std::vector<int32_t> codes;
+    HIP_TRY(dp.byte_marginals_logq_download(lq.data(), s));
+    ctx->dbm_mrow.clear();
+    ctx->dbm_midx.clear();
+    ctx->dbm_mval.clear();
+    if (rows) {
+        ctx->dbm_mrow = dp.byte_marginals_mrow();
+        ctx->dbm_midx.resize(size_t(entries));
+        ctx->dbm_mval.resize(size_t(entries));
+        HIP_TRY(dp.byte_marginals_rows_download(ctx->dbm_midx.data(), ctx->dbm_mval.data(), s));
+    }
+    if (decode) {
+        sc.assign(size_t(S), 0.0);
+        plw.assign(size_t(S), 0.0);
+        codes.assign(2 * size_t(off[size_t(S)] + S), wfsa::kCodeNone);
+        HIP_TRY(dp.byte_marginals_paths_download(sc.data(), plw.data(), codes.data(), s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (rows) dp.byte_marginals_rows_release();
+    auto span = [&](int i, int j, double& out) -> hipError_t {
+        float ms = 0.f;
+        const hipError_t r = hipEventElapsedTime(&ms, ctx->dbm_ev[i], ctx->dbm_ev[j]);
+        out = double(ms);
+        return r;
+    };
+    double fw = 0.0, bw = 0.0, r1 = 0.0, r2 = 0.0, dc = 0.0;
+    HIP_TRY(span(0, 1, fw));
+    HIP_TRY(span(1, 2, bw));
+    if (rows) {
+        HIP_TRY(span(2, 3, r1));
+        HIP_TRY(span(4, 5, r2));
+    }
+    if (decode) HIP_TRY(span(6, 7, dc));
+    ctx->stats.dense_bm_forward_ms = fw;
+    ctx->stats.dense_bm_backward_ms = bw;
+    ctx->stats.dense_bm_rows_ms = r1 + r2;
+    ctx->stats.dense_bm_decode_ms = dc;
+    ctx->stats.byte_marginal_ms = fw + bw + (r1 + r2) + dc;
+    ctx->dbm_prow.assign(size_t(S) + 1, 0);
+    ctx->dbm_pidx.clear();
+    if (decode)
+        for (int64_t i = 0; i < S; ++i) {
+            if (plw[size_t(i)] > -INFINITY) {
+                const int32_t* cd = codes.data() + 2 * (off[size_t(i)] + i);
+                const int64_t n = 2 * (off[size_t(i) + 1] - off[size_t(i)] + 1);
+                for (int64_t q = 0; q < n; ++q) {
+                    if (cd[q] == wfsa::kCodeNone || cd[q] >= np)
+                        return fail(WFSA_ERR_HIP, "%s: string %lld: code %d at entry %lld is not a path edge", name, (long long)i, int(cd[q]),
+                                    (long long)q);
+                    if (cd[q] >= 0) ctx->dbm_pidx.push_back(cd[q]);
+                }
+            }
+            ctx->dbm_prow[size_t(i) + 1] = int64_t(ctx->dbm_pidx.size());
+        }
+    ctx->dbm_has_rows = rows != 0;
+    ctx->dbm_has_path = decode != 0;
+    ctx->dbm_valid = true;
+    if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
+    if (decode && score && S > 0) std::memcpy(score, sc.data(), size_t(S) * sizeof(double));
+    if (decode && path_logw && S > 0) std::memcpy(path_logw, plw.data(), size_t(S) * sizeof(double));
+    if (n_entries) *n_entries = entries;
+    if (n_path_entries) *n_path_entries = int64_t(ctx->dbm_pidx.size());
+    return WFSA_OK;
+}
+
+int wfsa_dev_dense_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow, int32_t* midx, double* mval) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->dbm_valid)
+        return fail(WFSA_ERR_ARG, "dense_byte_marginals_get: no wfsa_dev_dense_byte_marginals result since the last load");
+    if (!ctx->dbm_has_rows) return fail(WFSA_ERR_ARG, "dense_byte_marginals_get: the last wfsa_dev_dense_byte_marginals call had rows = 0");
+    if (mrow) std::memcpy(mrow, ctx->dbm_mrow.data(), ctx->dbm_mrow.size() * sizeof(int64_t));
+    if (midx && !ctx->dbm_midx.empty()) std::memcpy(midx, ctx->dbm_midx.data(), ctx->dbm_midx.size() * sizeof(int32_t));
+    if (mval && !ctx->dbm_mval.empty()) std::memcpy(mval, ctx->dbm_mval.data(), ctx->dbm_mval.size() * sizeof(double));
+    return WFSA_OK;
+}
+
+int wfsa_dev_dense_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
+    if (!ctx) return fail(WFSA_ERR_ARG, "null context");
+    if (!ctx->dbm_valid)
+        return fail(WFSA_ERR_ARG, "dense_byte_marginals_path_get: no wfsa_dev_dense_byte_marginals result since the last load");
+    if (!ctx->dbm_has_path)
+        return fail(WFSA_ERR_ARG, "dense_byte_marginals_path_get: the last wfsa_dev_dense_byte_marginals call had decode = 0");
+    if (prow) std::memcpy(prow, ctx->dbm_prow.data(), ctx->dbm_prow.size() * sizeof(int64_t));
+    if (pidx && !ctx->dbm_pidx.empty()) std::memcpy(pidx, ctx->dbm_pidx.data(), ctx->dbm_pidx.size() * sizeof(int32_t));
     return WFSA_OK;
 }
 

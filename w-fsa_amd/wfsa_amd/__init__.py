@@ -830,6 +830,41 @@ class Device:
                                load().wfsa_dev_byte_marginals_path_get, check_dev, (self._h, _ptr(w)), self.n_strings,
                                int(off[-1]) if off is not None and len(off) else 0, decode)
 
+    def dense_byte_marginals(self, w_full, rows=True, decode=False):
+        """byte_marginals for a model on the dense path (stats()["dense"] == 1),
+        where byte_marginals has no trellis to walk: the same tuple (mrow,
+        midx, mval, boundary, logq[, score, path_logw, prow, pidx]) from the
+        evaluation's own forward and backward passes over the dense row slots.
+        Every interior state emits one byte there, so boundary is 1.0 after
+        every byte (NaN on the bytes of a string with logq -inf); logq carries
+        objective_grad's bytes; 0 < mval <= 1.  rows=False (with decode=True)
+        is the decode alone: empty rows, no 4 GiB limit on them.  MEA ties go
+        to the lowest state (byte_marginals: to the greater log weight)"""
+        w = np.ascontiguousarray(w_full, dtype=np.float64)
+        if w.size < self.n_params:
+            raise ValueError(f"w_full has {w.size} values, the model {self.n_params} parameters")
+        off = getattr(self, "_off", None)
+        n, nb = self.n_strings, int(off[-1]) if off is not None and len(off) else 0
+        m, mp = C.c_int64(), C.c_int64()
+        logq = np.zeros(n, dtype=np.float64)
+        score = np.zeros(n, dtype=np.float64) if decode else None
+        plw = np.zeros(n, dtype=np.float64) if decode else None
+        check_dev(load().wfsa_dev_dense_byte_marginals(self._h, _ptr(w), 1 if rows else 0, 1 if decode else 0, _ptr(logq), _ptr(score),
+                                                       _ptr(plw), C.byref(m), C.byref(mp)))
+        mrow = np.zeros(nb + 1, dtype=np.int64)
+        midx = np.zeros(max(m.value, 1), dtype=np.int32)
+        mval = np.zeros(max(m.value, 1), dtype=np.float64)
+        if rows:
+            check_dev(load().wfsa_dev_dense_byte_marginals_get(self._h, _ptr(mrow), _ptr(midx), _ptr(mval)))
+        boundary = np.repeat(np.where(logq > -np.inf, 1.0, np.nan), np.diff(np.asarray(off, dtype=np.int64))) if nb else np.zeros(0)
+        out = (mrow, midx[:m.value], mval[:m.value], boundary, logq)
+        if not decode:
+            return out
+        prow = np.zeros(n + 1, dtype=np.int64)
+        pidx = np.zeros(max(mp.value, 1), dtype=np.int32)
+        check_dev(load().wfsa_dev_dense_byte_marginals_path_get(self._h, _ptr(prow), _ptr(pidx)))
+        return out + (score, plw, prow, pidx[:mp.value])
+
     def comm_init(self, nranks, rank, unique_id):
         buf = (C.c_uint8 * _lib.COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))
         check_dev(load().wfsa_dev_comm_init(self._h, nranks, rank, buf))

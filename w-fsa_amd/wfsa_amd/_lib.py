@@ -59,6 +59,7 @@ class DevStats(C.Structure):
         ("dense_bp_tables_ms", dbl), ("dense_bp_forward_ms", dbl), ("dense_bp_backtrack_ms", dbl),
         ("qn_wave_launches", i64),
         ("dense_sp_forward_ms", dbl), ("dense_sp_backward_ms", dbl),
+        ("dense_bm_forward_ms", dbl), ("dense_bm_backward_ms", dbl), ("dense_bm_rows_ms", dbl), ("dense_bm_decode_ms", dbl),
     ]
 
 
@@ -97,6 +98,9 @@ _SIGS = {
     "wfsa_dev_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
     "wfsa_dev_dense_sample_paths": (C.c_int, [vp, vp, C.c_int32, C.c_uint64, vp, P(i64), P(i64)]),
     "wfsa_dev_dense_sample_paths_get": (C.c_int, [vp, vp, vp, vp, vp]),
+    "wfsa_dev_dense_byte_marginals": (C.c_int, [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, P(i64), P(i64)]),
+    "wfsa_dev_dense_byte_marginals_get": (C.c_int, [vp, vp, vp, vp]),
+    "wfsa_dev_dense_byte_marginals_path_get": (C.c_int, [vp, vp, vp]),
     "wfsa_dev_generate": (C.c_int, [vp, vp, i64, C.c_int32, C.c_uint64, P(i64), P(i64), vp]),
     "wfsa_dev_generate_get": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
     "wfsa_dev_posterior_counts": (C.c_int, [vp, vp, vp, vp, P(i64)]),
