@@ -150,6 +150,8 @@ typedef struct {
      * forward pass, the backward pass, the count and fill kernels (0 with
      * rows = 0), the tables, reward steps and back-track (0 with decode = 0) */
     double dense_bm_forward_ms, dense_bm_backward_ms, dense_bm_rows_ms, dense_bm_decode_ms;
+    int64_t bubble_grid_launches; /* of ll_dot_launches, those launched as a grid of only the waves that have work (step_grid_kernel; WFSA_BUBBLE_GRID=0, the rmin column or the in-kernel QN update: none) */
+    int32_t stream_grid;       /* blocks of the stream kernel's geometry (stream_block threads each); the bubble-grid launch's roles are waves of it */
 } wfsa_dev_stats;
 
 /* context ---------------------------------------------------------------- */

@@ -3745,6 +3745,100 @@ __global__ __launch_bounds__(1024) void step_dot_kernel(CompiledArgs a) {
 #undef WFSA_STAMP
 }
 
+// step_dot_kernel<false, false, false> with only the waves that have work
+// (BubbleGrid, fb_kernels.hpp): real wave r of the grid runs role r -- the
+// bubbles, the big-bubble rank and the dot-product terms of one (block, wave)
+// of step_dot_kernel's geometry, through the same device functions, so every
+// slot and every wave partial has that launch's bits.  The roles come longest
+// first, so with in-order block dispatch the class-B chunks start first, one
+// to a SIMD, and the shorter roles fill in behind them.  No block barrier and
+// no LDS counter: a wave stores its partial to wpart (summed per block by the
+// kernel after this one, LlFold), and a big-bubble role stages in its own
+// wave's LDS.  The per-edge weights are strided over the real grid (every
+// element written once, by one thread).  No wave priorities: a long role
+// has a SIMD's issue nearly to itself, and step_dot_kernel's priorities only
+// held its neighbours back (16.1-16.3 against 15.4-15.5 us per step,
+// profiles/bubble_grid/sweep.txt).
+// (four waves a SIMD, step_dot_kernel's register budget: the short roles fill in beside the long ones)
+__global__ __launch_bounds__(kGridBlock) __attribute__((amdgpu_waves_per_eu(4))) void step_grid_kernel(CompiledArgs a,
+                                                                                                      BubbleGrid g) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int lane = lane_id();
+    const int rw = __builtin_amdgcn_readfirstlane(int(threadIdx.x) / kWave);   // the wave in the (real) block
+    const int ri = __builtin_amdgcn_readfirstlane(int(blockIdx.x) * (kGridBlock / kWave) + rw);
+    // One round of scalar loads at the entry: the wave's role, the bubble
+    // arguments and the halt flag together -- the role is a load ahead of
+    // everything the wave does, and the bubbles' first loads wait for nothing
+    // else (step_dot_kernel reads the flag, passes its barrier and then
+    // fetches the arguments: three rounds).  The asm pins the loads above the
+    // flag's branch.
+    const BubbleRole role = g.roles[min(ri, g.n_roles - 1)];   // (wave-uniform; past the roles: unused)
+    const BubbleArgs bub = WFSA_LATE_ARG(bub);
+    // halted is written only by an earlier launch (the QN step's finish)
+    const unsigned halt = a.halted ? *a.halted : 0u;
+    asm volatile("" ::"s"(role.bid), "s"(role.rank_flags), "s"(bub.n_small4), "s"(bub.sm_tbl), "s"(bub.contrib),
+                 "s"(bub.ewp), "s"(bub.wt));
+    if (halt) return;
+    if (ri < g.n_roles) {
+        const int bid = role.bid, w = role.wave;
+        const int nblk = g.vblk, wpb = g.vwpb;
+        const int nw = nblk * wpb;
+        const int gw = bid * wpb + w;
+#ifdef WFSA_EXPERIMENTS
+        unsigned long long* tr = a.trace ? a.trace + size_t(gw) * 16 : nullptr;   // (timing experiments)
+#define WFSA_STAMP(k) \
+    if (tr && lane == 0) tr[k] = __builtin_amdgcn_s_memrealtime();
+#else
+#define WFSA_STAMP(k)
+#endif
+        WFSA_STAMP(0)
+        double ll_acc = ll_trivial_share(a.ll_coef, a.w, a.n_params, gw * kWave + lane, nw * kWave);
+        WFSA_STAMP(1)
+        const bool fin_wave = (role.rank_flags & kRoleFin) != 0;
+        if (fin_wave && a.fin.active) {   // the previous QN step's finish (step_dot_kernel's finish wave)
+            double finfo[7];
+            unsigned fstat = kQnRan;
+            const QnFinish fin = WFSA_LATE_ARG(fin);
+            qn_finish_compute<true, false, false>(fin, nullptr, finfo, fstat);
+            if (lane == 0) qn_finish_publish(fin, finfo, fstat);
+        }
+        if (a.bub_on && !fin_wave) {   // step_dot_kernel's deal: the same chunks, the same ranks
+            if (role.chunk >= 0) {
+                const int b = int(small_entry(role.chunk, lane, bub.n_small4, bub.n_small));
+#ifdef WFSA_EXPERIMENTS
+                unsigned long long* btr = tr;
+#else
+                unsigned long long* btr = nullptr;
+#endif
+                if (b >= 0 && b < bub.n_small4)
+                    ll_acc += small_bubble<4, 4, false, false, false, true>(bub, bub.sm4_tbl, bub.n_small4, b, b, btr, nullptr, nullptr);
+                else if (b >= bub.n_small4)
+                    ll_acc += small_bubble<8, 8, false, false, false, true>(bub, bub.sm_tbl, bub.n_small, b - bub.n_small4, b, btr, nullptr, nullptr);
+            }
+            const int r = role.rank_flags >> 8;
+            if (r < bub.n_big) {
+                const int E = bub.big_lds_edges;
+                char* stg = reinterpret_cast<char*>(lds) + rw * big_stage_bytes(E);
+                double* lw = reinterpret_cast<double*>(stg);
+                int* lsd = reinterpret_cast<int*>(lw + E + 2 * kMaxBubbleNodes);
+                RminLane rm_big{0.0, -1, 0, 0, -1};
+                double rm_cv = INFINITY, rm_ci = -1.0;
+                for (int i = r; i < bub.n_big; i += nw - 1)
+                    ll_acc += big_bubble(bub, i, lsd, lw, lw, lw + E, nullptr, &rm_cv, &rm_ci, &rm_big);
+            }
+        }
+        WFSA_STAMP(2)
+        WFSA_STAMP(4)
+        ll_acc = wave_sum(ll_acc);
+        if (lane == 0) g.wpart[gw] = ll_acc;
+        WFSA_STAMP(7)
+#undef WFSA_STAMP
+    }
+    // this (real) block's slice of the per-edge weights and the zeroed
+    // result, for the kernels after this one
+    if (a.tables >= 1 && !a.no_slice) edge_weight_slice(a, int(blockIdx.x), int(gridDim.x));
+}
+
 // Group headers (stream_hdr_words), written after the streams are emitted:
 // lane l's first chunk of group g gets p of its string and the group's row
 // count; the string's words follow in the same chunk.
@@ -3794,6 +3888,10 @@ __global__ __launch_bounds__(kReduceBlock) void reduce_kernel(ReduceArgs a) {
     const int tb = int(blockIdx.x);
     if (tb == a.n_tiles) {   // log-likelihood, fixed order
         __shared__ double red[kReduceBlock];
+        if (a.fold.wpart) {   // the bubble-grid launch's block partials first (thread t reads back its own entries)
+            ll_fold(a.fold, t, kReduceBlock);
+            __syncthreads();
+        }
         red[t] = strided_sum(a.ll_part, a.n_ll, t, kReduceBlock);
         __syncthreads();
         for (int w = kReduceBlock / 2; w > 0; w >>= 1) {
@@ -4299,6 +4397,25 @@ hipError_t launch_step_dot(const CompiledArgs& a, int grid, int block, size_t ld
     if (a.bub_on && a.bub.rmin_acc)
         return go(step_dot_kernel<true, false, false>, grid, block, lds, stream, ev0, ev1, a);
     return go(step_dot_kernel<false, false, false>, grid, block, lds, stream, ev0, ev1, a);
+}
+
+hipError_t launch_step_grid(const CompiledArgs& a, const BubbleGrid& g, size_t wave_lds, hipStream_t stream,
+                            hipEvent_t ev0, hipEvent_t ev1) {
+    if (a.qw.on || a.rf.part || (a.bub_on && a.bub.rmin_acc) || g.n_roles <= 0 || !g.roles || !g.wpart)
+        return hipErrorInvalidValue;   // (those variants need step_dot_kernel's geometry)
+    if (ev0 || ev1) {   // no dispatch events inside a stream capture (the graph path records none)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) ev0 = ev1 = nullptr;
+    }
+    constexpr int WPB = kGridBlock / kWave;
+    int64_t blocks = (int64_t(g.n_roles) + WPB - 1) / WPB;
+    // the per-edge weights, when this launch writes them, keep step_dot_kernel's thread count
+    if (a.tables >= 1 && !a.no_slice) blocks = std::max(blocks, int64_t(g.vblk) * g.vwpb / WPB);
+    const dim3 gd{unsigned(blocks), 1, 1}, bd{unsigned(kGridBlock), 1, 1};
+    const size_t lds = size_t(WPB) * wave_lds;
+    if (ev0 || ev1) hipExtLaunchKernelGGL(step_grid_kernel, gd, bd, uint32_t(lds), stream, ev0, ev1, 0u, a, g);
+    else hipLaunchKernelGGL(step_grid_kernel, gd, bd, lds, stream, a, g);
+    return hipGetLastError();
 }
 
 int step_dot_blocks_per_cu(int block, size_t lds, bool rmin, bool px) {

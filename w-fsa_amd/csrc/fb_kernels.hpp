@@ -502,6 +502,28 @@ struct QnFinish {
     unsigned* host_flag;         // host-mapped completion flag
     double* host_ring;           // host-mapped [slots][kQnRow]
 };
+// The block partials of the bubble-grid step launch (BubbleGrid below), summed
+// by a few threads at the front of the kernel that follows it: ll_part[b] for
+// b = first, first + stride, ... below nblk is block b's wave partials added in
+// wave order from 0.0 (step_dot_kernel's writer: the same bits).
+constexpr int kFoldWaves = 16;   // waves of a 1024-thread block: the most a block has
+struct LlFold {
+    const double* wpart;         // [nblk * wpb], or null: nothing to fold
+    double* ll_part;             // [nblk]
+    int32_t nblk, wpb;
+};
+__device__ __forceinline__ void ll_fold(const LlFold& f, int first, int stride) {
+    for (int b = first; b < f.nblk; b += stride) {
+        const double* p = f.wpart + size_t(b) * size_t(f.wpb);
+        double v[kFoldWaves], t = 0.0;   // (the loads in one round)
+#pragma unroll
+        for (int i = 0; i < kFoldWaves; ++i) v[i] = p[min(i, f.wpb - 1)];
+#pragma unroll
+        for (int i = 0; i < kFoldWaves; ++i)
+            if (i < f.wpb) t += v[i];
+        f.ll_part[b] = t;
+    }
+}
 struct QnArgs {
     const double* out;           // [1 + n_full]: gradient parts accumulated so far
     double* ll_stash;            // non-null (across ranks): out[0], the step's all-reduced log-likelihood,
@@ -535,6 +557,7 @@ struct QnArgs {
     int32_t chunk_cap;           // ... and its slot chunks (<= kMaxChunks; 0: that)
     RminArgs rm;                 // rm_on: the rmin strings pass folded into this launch (its block c runs
     int32_t rm_on, rm_blocks;    // the pass's block c, c < rm_blocks; the grid covers both)
+    LlFold fold;                 // fold.wpart: the bubble-grid launch's wave partials, summed into ll_part first
 };
 
 // Bubble evaluation.  Contributions (-p_s x edge posterior) go straight to
@@ -811,6 +834,33 @@ struct CompiledArgs {
 };
 
 
+// The bubble-grid form of the stream-less step launch (step_grid_kernel, the
+// <RMIN, QN, PX> = <false, false, false> case only: no in-kernel hand-off
+// needs the stream kernel's geometry there).  Only the waves of that geometry
+// that have work are launched, one wave per *role*, longest first: role r is
+// the virtual (block, wave) whose bubble chunk, big-bubble rank and
+// dot-product terms it runs -- the same lanes, slots and sums as in
+// step_dot_kernel.  A role stores its log-likelihood partial to
+// wpart[block * waves per block + wave]; waves without a role are never
+// launched and their entries stay zero (zeroed at preparation).  The kernel
+// that follows (LlFold) sums a block's entries into ll_part[block] in wave
+// order from 0.0, as step_dot_kernel's last wave does.
+constexpr int kRoleFin = 1;      // the finish wave (block 0's last): the previous QN step's finish, no bubbles
+struct BubbleRole {              // 16 bytes, read as one scalar load
+    int32_t bid, wave;           // the virtual block and wave in the block
+    int32_t chunk;               // small-bubble chunk (small_entry), or -1
+    int32_t rank_flags;          // big_rank << 8 | kRole flags (a rank >= n_big: no big bubble)
+};
+struct BubbleGrid {
+    const BubbleRole* roles;
+    int32_t n_roles;
+    int32_t vblk, vwpb;          // the virtual geometry: blocks, waves per block
+    double* wpart;               // [vblk * vwpb]
+};
+// threads per block of the bubble-grid launch: a wave per SIMD (64 and 128 measured the same within the
+// runs' spread, profiles/bubble_grid/sweep.txt)
+constexpr int kGridBlock = 256;
+
 // The per-iteration reduction, one launch, deterministic: parameters in
 // slot order are cut into tiles (consecutive positions, bounded slots); a
 // block per tile adds to out[1 + j] the constant trivial-word gradient (when
@@ -839,6 +889,7 @@ struct ReduceArgs {
     int32_t n_ll;
     double* out;                 // [1 + n_params]
     const unsigned* halted;
+    LlFold fold;                 // fold.wpart: the bubble-grid launch's wave partials, summed into ll_part first
 };
 // Completion without a DMA copy or a stream synchronisation: a one-block
 // kernel copies out[0, n) into host-mapped memory (adding `add` to out[1..]
@@ -902,6 +953,10 @@ int fbs_qn_blocks_per_cu(int block, size_t lds);
 // blocks of its in-kernel QN variant one CU holds (rmin: the folded column, px: the exchange across ranks)
 hipError_t launch_step_dot(const CompiledArgs& a, int grid, int block, size_t lds, hipStream_t stream,
                            hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// its bubble-grid form (step_grid_kernel: a without rmin column, QN update and exchange), a wave per role in
+// blocks of kGridBlock threads; wave_lds: a wave's big-bubble staging in bytes (0: no big bubble)
+hipError_t launch_step_grid(const CompiledArgs& a, const BubbleGrid& g, size_t wave_lds, hipStream_t stream,
+                            hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 int step_dot_blocks_per_cu(int block, size_t lds, bool rmin, bool px);
 hipError_t launch_bubbles(const BubbleArgs& a, hipStream_t stream);
 hipError_t launch_reduce(const ReduceArgs& a, hipStream_t stream);
@@ -921,7 +976,8 @@ hipError_t launch_stage(const double* host_w, double* w, double* ewp, int32_t n,
 hipError_t launch_qn_step(const QnArgs& a, bool fused, hipStream_t stream);
 // the fused update a wave per constraint instead of a block (qn_wave_kernel, qn_kernel.hip; the same bits): every
 // constraint with 1 to kQnWaveMembers members and at most kQnWaveMaxChunks slot chunks, a.contrib and a.fixed_t
-// set, no rmin strings pass folded in (a.rm_on) and no a.ll_stash; grid ceil(k / 4)
+// set, no rmin strings pass folded in (a.rm_on) and no a.ll_stash; grid ceil(k / 4), and with a.fold.wpart
+// blocks of their own behind them that sum the bubble-grid launch's block partials
 constexpr int kQnWaveMaxChunks = 64 * kQnWaveChunkRounds;
 hipError_t launch_qn_wave(const QnArgs& a, hipStream_t stream);
 // dst[i] = src[idx[i]], i < n

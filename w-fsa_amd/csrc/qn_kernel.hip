@@ -69,7 +69,8 @@ __global__ __launch_bounds__(NT) void qn_step_kernel(QnArgs a) {
         }
     }
     // halted and halt_pending are written only by earlier launches: every
-    // block of this one sees the same values
+    // block of this one sees the same values (block 0's store below rewrites
+    // halted[0] only where this test already holds)
     if (a.halted[0] || a.halted[1]) {   // a step enqueued after the halt: published as skipped
         if (c == 0 && t == 0) {
             a.halted[0] = 1u;   // for the evaluation kernels of the later steps
@@ -77,6 +78,10 @@ __global__ __launch_bounds__(NT) void qn_step_kernel(QnArgs a) {
         }
         return;
     }
+    // the bubble-grid launch's block partials (LlFold), for a later launch's
+    // finish, strided over the grid's threads.  A skipped step has no finish,
+    // so nothing reads its ll_part: the sum is left out with the update.
+    if (a.fold.wpart) ll_fold(a.fold, c * NT + t, int(gridDim.x) * NT);
     if (a.ll_stash && c == 0 && t == 0) *a.ll_stash = a.out[0];
     if (a.rm_on && c < a.rm_blocks) {   // the rmin strings pass's block c (one launch fewer per step)
         static_assert(kRminBlock == kQnBlock, "the folded rmin pass runs in the QN step's blocks");
@@ -257,8 +262,24 @@ __device__ __forceinline__ double qn_dpp(double v) {   // v of the lane CTRL nam
     hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
+// The block partials of the bubble-grid step launch (LlFold), off the
+// constraints' path: the grid's blocks past the constraints' (launch_qn_wave
+// adds them), a thread per block partial (ll_fold).  Inside the constraint
+// waves the sum lengthened the kernel: by 0.65 us as lane shuffles at the
+// waves' end, and no less as loads at their entry (profiles/bubble_grid).
+// The reader of ll_part is a later launch (the next step's finish, or the
+// flush); a skipped step (either halt word set -- the constraint waves' own
+// test, on which every block agrees: wave 0 rewrites halted[0] only where the
+// test already holds) has no finish, so its sum is left out with the update.
+__device__ __forceinline__ int qn_wave_blocks(int k) { return (k + kQnBlock / 64 - 1) / (kQnBlock / 64); }
 __global__ __launch_bounds__(kQnBlock) void qn_wave_kernel(QnArgs a) {
     if (WFSA_KDBG(a.dbg) == 3) return;   // (timing experiments: the launch alone)
+    if (int(blockIdx.x) >= qn_wave_blocks(a.k)) {
+        if (a.fold.wpart && !(a.halted[0] || a.halted[1]))
+            ll_fold(a.fold, (int(blockIdx.x) - qn_wave_blocks(a.k)) * kQnBlock + int(threadIdx.x),
+                    (int(gridDim.x) - qn_wave_blocks(a.k)) * kQnBlock);
+        return;
+    }
     __shared__ __attribute__((aligned(16))) double wlds[kQnBlock / 64][kQnWaveLds];
     const int lane = int(threadIdx.x) & 63;
     const int wv = __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6);
@@ -413,7 +434,9 @@ hipError_t launch_qn_wave(const QnArgs& a_in, hipStream_t stream) {
     QnArgs a = a_in;
     a.dbg = dbg;
     constexpr int WPB = kQnBlock / 64;
-    hipLaunchKernelGGL(qn_wave_kernel, dim3(unsigned((a.k + WPB - 1) / WPB)), dim3(kQnBlock), 0, stream, a);
+    // (the bubble-grid launch's block partials: blocks of their own behind the constraints')
+    const int fold_blocks = a.fold.wpart ? (a.fold.nblk + kQnBlock - 1) / kQnBlock : 0;
+    hipLaunchKernelGGL(qn_wave_kernel, dim3(unsigned((a.k + WPB - 1) / WPB + fold_blocks)), dim3(kQnBlock), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -422,6 +422,14 @@ struct wfsa_dev {
     // qn_kernel.hip) instead of qn_step_kernel's block per constraint
     bool use_qn_wave = true;         // WFSA_QN_WAVE=0: qn_step_kernel
     bool qnw_ok = false;             // this Run: every constraint fits a wave (qn_run_impl)
+    // the stream-less step launch without rmin column, QN update and exchange
+    // as a grid of its waves that have work (step_grid_kernel, fb_kernels.hip;
+    // the roles and the zeroed wave partials are written at preparation)
+    bool use_bubble_grid = true;     // WFSA_BUBBLE_GRID=0: step_dot_kernel's geometry
+    DevBuf<wfsa::BubbleRole> grid_roles;
+    DevBuf<double> grid_wpart;       // [i_grid * waves per block]
+    int32_t grid_n_roles = 0;
+    wfsa::LlFold fold_pending{};     // the launch's block partials: summed by the next reduction or QN kernel
     DevBuf<unsigned long long> fbs_trace;   // timing experiments (WFSA_FBS_TRACE): per-wave stamps of the last launch
 
     // dense automata: the fp64 MFMA path (dense_path.hpp) replaces the
@@ -1098,6 +1106,84 @@ int small_waves_per_block(int64_t n_small, int nblk) {
 }
 // byte offset of the big bubbles' staging in the stream kernel's LDS (after w)
 size_t big_stage_off(const wfsa_dev* ctx) { return (ctx->i_lds + 15) & ~size_t(15); }
+
+// The bubble-grid launch's roles (wfsa::BubbleGrid, fb_kernels.hpp): the waves
+// of the per-iteration geometry (i_grid blocks of i_block threads) that have
+// work in the stream-less step launch, each with the chunk, the big-bubble
+// rank and the (block, wave) it has there.  The finish wave leads (one wave;
+// the previous step's row waits for it); then, longest first, the class-B
+// chunks -- by the structure ids among their lanes, descending: a wave runs a
+// sweep turn per id -- the big-bubble ranks by their bubbles' edges,
+// descending, the class-A chunks, and the waves that hold only terms of the
+// dot product.  The wave partials are zeroed here once: a wave without a role
+// is never launched and no role writes its entry.  (The big-bubble ranks
+// first, or the geometry's own wave order, measured no better:
+// profiles/bubble_grid/sweep.txt.)
+int build_bubble_grid(wfsa_dev* ctx) {
+    ctx->grid_n_roles = 0;
+    const int nblk = ctx->i_grid, wpb = ctx->i_block / kWave;
+    const int64_t nw = int64_t(nblk) * wpb;
+    if (!ctx->use_bubble_grid || ctx->n_groups <= 0 || nblk <= 0 || wpb <= 0 || wpb > wfsa::kFoldWaves ||
+        nw >= (int64_t(1) << 22))
+        return WFSA_OK;
+    hipStream_t s = ctx->stream;
+    const bool bub = bubbles_fused(ctx, false);
+    const int64_t n4 = ctx->n_small4, ns = ctx->n_small;
+    const int64_t na = (n4 + kWave - 1) / kWave, nch = bub ? wfsa::small_chunks(n4, ns) : 0;
+    const int small_wpb = small_waves_per_block(nch * kWave, nblk);
+    const int64_t dot_waves = (int64_t(ctx->n_params) + kWave - 1) / kWave;   // (ll_trivial_share: waves with a term)
+    // a class-B chunk's structure ids (layout_slots' table headers carry the same)
+    std::vector<int32_t> turns(size_t(std::max<int64_t>(nch - na, 0)), 1);
+    for (size_t cb = 0; bub && cb < turns.size(); ++cb) {
+        std::vector<int> ids;
+        for (int64_t b = int64_t(cb) * kWave; b < std::min<int64_t>(ns, int64_t(cb + 1) * kWave); ++b) {
+            const int32_t o = ctx->h_sm_list[size_t(b)];
+            ids.push_back(ctx->use_bubble_shapes ? wfsa::bubble_shape_id(wfsa::kBubbleRegEdges, ctx->h_bubbuf[size_t(o)],
+                                                                         &ctx->h_bubbuf[size_t(o) + 5], 2)
+                                                 : 0);
+        }
+        std::sort(ids.begin(), ids.end());
+        turns[cb] = int32_t(std::unique(ids.begin(), ids.end()) - ids.begin());
+    }
+    struct Keyed {
+        wfsa::BubbleRole r;
+        int group;
+        int64_t key, gw;
+    };
+    std::vector<Keyed> list;
+    for (int64_t gw = 0; gw < nw; ++gw) {
+        const int bid = int(gw / wpb), w = int(gw % wpb);
+        const bool fin = bid == 0 && w == wpb - 1;
+        Keyed k{{bid, w, -1, 0}, 4, 0, gw};
+        int64_t rank = (int64_t(1) << 22);   // (no bubbles in the launch: never below n_big)
+        if (bub && !fin) {
+            const int64_t ch = int64_t(w) * nblk + bid;   // (wfsa::small_entry's chunks)
+            if (w < small_wpb && ch < nch) k.r.chunk = int32_t(ch);
+            rank = wfsa::big_rank(bid, w, nblk, wpb, ctx->qw_waves);
+        }
+        int64_t big_edges = 0;
+        for (int64_t i = rank; i < ctx->n_big; i += nw - 1) big_edges += ctx->h_bubbuf[size_t(ctx->h_big_list[size_t(i)])] >> 16;
+        const bool class_b = k.r.chunk >= 0 && k.r.chunk >= na;
+        k.r.rank_flags = int32_t(rank << 8) | (fin ? wfsa::kRoleFin : 0);
+        if (fin) k.group = 0;
+        else if (class_b) k.group = 1, k.key = turns[size_t(k.r.chunk - na)];
+        else if (rank < ctx->n_big) k.group = 2, k.key = big_edges;
+        else if (k.r.chunk >= 0) k.group = 3;
+        else if (gw >= dot_waves) continue;   // nothing to do: not launched
+        list.push_back(k);
+    }
+    std::stable_sort(list.begin(), list.end(), [](const Keyed& x, const Keyed& y) {
+        return x.group != y.group ? x.group < y.group : x.key > y.key;
+    });
+    std::vector<wfsa::BubbleRole> roles;
+    for (const Keyed& k : list) roles.push_back(k.r);
+    HIP_TRY(ctx->grid_roles.upload(roles.data(), roles.size(), s));
+    HIP_TRY(ctx->grid_wpart.alloc(size_t(nw)));
+    HIP_TRY(hipMemsetAsync(ctx->grid_wpart.ptr, 0, size_t(nw) * sizeof(double), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ctx->grid_n_roles = int32_t(roles.size());
+    return WFSA_OK;
+}
 
 // per-kernel timing events of slot `slot` (< 0: this launch is not timed;
 // WFSA_TIMING=0 leaves them all out).  An event between two kernels costs a
@@ -2212,6 +2298,7 @@ int prepare(wfsa_dev* ctx, int level) {
     ctx->ll_stride = waves;
     ctx->ll_cur = ctx->ll_part.ptr;
     HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = build_bubble_grid(ctx)) return rc;
 
     // the trivial words' gradient, once: compiled pass with gradient at
     // w = 0 (its log-weights are discarded), then the slab sum
@@ -2252,6 +2339,7 @@ int prepare(wfsa_dev* ctx, int level) {
     ctx->stats.tier1_strings = n_tier1;
     ctx->stats.waves_per_block = ctx->cfg[0].waves_per_block;
     ctx->stats.stream_block = ctx->i_block;
+    ctx->stats.stream_grid = ctx->i_grid;
     ctx->stats.stream_w_lds = ctx->i_tables;
     ctx->stats.stream_wide = ctx->wide ? 1 : 0;
     ctx->stats.stream_multi = ctx->n_multi > 0 ? 1 : 0;
@@ -2366,6 +2454,23 @@ int enqueue_compiled(wfsa_dev* ctx, bool with_grad, bool want_logq, const unsign
             HIP_TRY(hipMemsetAsync(ctx->gpart.ptr, 0, size_t(ctx->c_grid) * size_t(np) * sizeof(double), s));
         if (with_grad) {
             HIP_TRY(wfsa::launch_compiled(c, ctx->c_grid, kGradBlock, lds, s));
+        } else if (dot && ctx->grid_n_roles > 0 && !c.qw.on && !c.rf.part && !ctx->rm_eval && !ctx->comm) {
+            // (one rank, no rmin pass in the evaluation, no QN update in the launch: the other steps keep
+            // step_dot_kernel's geometry)
+            // step_dot_kernel<false, false, false>'s work as a grid of its waves that have any; the
+            // block partials are summed by the kernel that follows (the reduction, or the QN update)
+            wfsa::BubbleGrid g{};
+            g.roles = ctx->grid_roles.ptr;
+            g.n_roles = ctx->grid_n_roles;
+            g.vblk = ctx->i_grid;
+            g.vwpb = ctx->i_block / kWave;
+            g.wpart = ctx->grid_wpart.ptr;
+            const size_t wave_lds = (c.bub_on && ctx->n_big > 0) ? size_t(wfsa::big_stage_bytes(ctx->big_lds_edges)) : 0;
+            HIP_TRY(wfsa::launch_step_grid(c, g, wave_lds, s, ktimed ? ctx->k0[slot] : nullptr,
+                                           ktimed ? ctx->kc[slot] : nullptr));
+            ctx->fold_pending = wfsa::LlFold{g.wpart, ctx->ll_cur, g.vblk, g.vwpb};
+            ++ctx->stats.ll_dot_launches;
+            ++ctx->stats.bubble_grid_launches;
         } else if (dot) {
             HIP_TRY(wfsa::launch_step_dot(c, ctx->i_grid, ctx->i_block, lds, s, ktimed ? ctx->k0[slot] : nullptr,
                                           ktimed ? ctx->kc[slot] : nullptr));
@@ -2459,6 +2564,8 @@ wfsa::ReduceArgs reduce_args(wfsa_dev* ctx, const unsigned* halted, int32_t n_ll
     r.n_ll = n_ll;
     r.out = ctx->out.ptr;
     r.halted = halted;
+    r.fold = ctx->fold_pending;   // (the bubble-grid launch of this evaluation: consumed)
+    ctx->fold_pending = wfsa::LlFold{};
     return r;
 }
 
@@ -3124,6 +3231,12 @@ int enqueue_qn_step(wfsa_dev* ctx, double eta, double tol, int64_t e, bool timed
     // qn_step_kernel, a block per constraint.
     const bool wave = !inkern && fused && ctx->use_qn_wave && ctx->qnw_ok && ctx->fixed_t_on && !q.rm_on &&
                       q.contrib != nullptr && !q.ll_stash;
+    // the bubble-grid launch's block partials, unless the reduction summed
+    // them: complete before their first reader, the next step's finish (in
+    // its step launch, or the flush)
+    q.fold = ctx->fold_pending;
+    ctx->fold_pending = wfsa::LlFold{};
+    if (q.fold.wpart && inkern) return fail(WFSA_ERR_HIP, "the bubble-grid launch's partials have no kernel to sum them");
     if (wave) {
         HIP_TRY(wfsa::launch_qn_wave(q, s));
         ++ctx->stats.qn_wave_launches;
@@ -3331,6 +3444,7 @@ int wfsa_dev_create(int device, wfsa_dev** out) {
     if (const char* e = std::getenv("WFSA_QN_WAVE")) ctx->use_qn_wave = e[0] != '0';
     if (const char* e = std::getenv("WFSA_LL_DOT")) ctx->use_ll_dot = e[0] != '0';
     if (const char* e = std::getenv("WFSA_BUBBLE_SHAPES")) ctx->use_bubble_shapes = e[0] != '0';
+    if (const char* e = std::getenv("WFSA_BUBBLE_GRID")) ctx->use_bubble_grid = e[0] != '0';
 
     HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&ctx->ev0));

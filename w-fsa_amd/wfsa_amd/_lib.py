@@ -60,6 +60,7 @@ class DevStats(C.Structure):
         ("qn_wave_launches", i64),
         ("dense_sp_forward_ms", dbl), ("dense_sp_backward_ms", dbl),
         ("dense_bm_forward_ms", dbl), ("dense_bm_backward_ms", dbl), ("dense_bm_rows_ms", dbl), ("dense_bm_decode_ms", dbl),
+        ("bubble_grid_launches", i64), ("stream_grid", i32),
     ]
 
 
