@@ -125,15 +125,48 @@ constexpr int kQnDepth = 8;   // device-resident QN steps in flight
 // weights after the results in the host-mapped buffer, 16-byte aligned
 inline size_t weights_off(int32_t np) { return (size_t(np) + 3) & ~size_t(1); }
 
-// what one decode entry point keeps on the device (decode.hpp): its own
-// weights, edge log-weights, per-wave scratch, work counter and results, and
-// the events that time its kernels
+// what one trellis entry point keeps on the device (decode.hpp): its own
+// weights (and their host copy, the zero slot last, alive while the upload
+// runs), edge log-weights, per-wave scratch, work counter and results, and the
+// events that time its kernels
 struct DecodeBufs {
+    std::vector<double> hw;
     DevBuf<double> w, lw, score, best;
     DevBuf<int32_t> back, path;
     DevBuf<unsigned> ctr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool valid = false;   // the host holds a result of this entry point for _get
+    hipEvent_t ev[2] = {};
+};
+
+template <class T>
+void copy_vec(T* dst, const std::vector<T>& v) {
+    if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(T));
+}
+
+// An entry point's last paths, on the host for _get, as Fsa parameter lists:
+// prow[S + 1], pidx (best_paths_get's layout; srow and logw stay empty), or
+// srow[S + 1], logw[P], prow[P + 1], pidx (kbest_paths_get's)
+struct PathResult {
+    std::vector<int64_t> srow, prow;
+    std::vector<double> logw;
+    std::vector<int32_t> pidx;
+    void copy_out(int64_t* srow_o, double* logw_o, int64_t* prow_o, int32_t* pidx_o) const {
+        copy_vec(srow_o, srow);
+        copy_vec(logw_o, logw);
+        copy_vec(prow_o, prow);
+        copy_vec(pidx_o, pidx);
+    }
+};
+
+// ... and its last sparse rows: row[R + 1], idx, val
+struct RowResult {
+    std::vector<int64_t> row;
+    std::vector<int32_t> idx;
+    std::vector<double> val;
+    void copy_out(int64_t* row_o, int32_t* idx_o, double* val_o) const {
+        copy_vec(row_o, row);
+        copy_vec(idx_o, idx);
+        copy_vec(val_o, val);
+    }
 };
 
 }  // namespace
@@ -457,72 +490,58 @@ struct wfsa_dev {
     int64_t hft_stride = 0;
     int32_t hft_vm = 0;
 
-    // The decodes (wfsa_dev_best_paths, wfsa_dev_kbest_paths; decode.hpp).
-    // Each entry point has buffers of its own, so a best_paths result and a
-    // kbest_paths result live side by side; the last call's paths as Fsa
-    // parameter lists stay on the host for _get
+    // The per-string features.  Each has one member: its device buffers and
+    // events, so that results of different features live side by side, its last
+    // result on the host for _get (PathResult / RowResult) and `valid`: the host
+    // holds a result of the entry point since the last load.
     int32_t max_dst = 1;         // the most destinations of one byte (model)
     int64_t n_in_edges = 0;      // in-edges over all bytes (model): a K-best back-pointer packs one with a rank
-    DecodeBufs bp, kb;
-    // The sampler (wfsa_dev_sample_paths; sample.hpp): a third buffer set, plus
-    // what the forward pass keeps beside it -- the stored rows and log q -- and
-    // its last result for _get, in kbest_paths_get's layout
-    DecodeBufs sp;
-    DevBuf<double> sp_hist, sp_logq;
-    std::vector<int64_t> sp_srow, sp_prow;
-    std::vector<double> sp_logw;
-    std::vector<int32_t> sp_pidx;
-    // Posterior expected counts (wfsa_dev_posterior_counts; posterior.hpp): a
-    // fourth buffer set, plus the stored rows, the fixed-point gamma and count
-    // rows, log q, entropy, the cursor and the rows as the waves left them --
-    // and its last result for _get, rows in string order
-    DecodeBufs pc;
-    DevBuf<double> pc_hist, pc_logq, pc_ent, pc_val;
-    DevBuf<unsigned long long> pc_gamma, pc_count, pc_cursor;
-    DevBuf<int64_t> pc_start;
-    DevBuf<int32_t> pc_len, pc_idx;
-    std::vector<int64_t> pc_crow;
-    std::vector<int32_t> pc_cidx;
-    std::vector<double> pc_cval;
+    // The decodes (wfsa_dev_best_paths, wfsa_dev_kbest_paths; decode.hpp)
+    struct DecodePaths {
+        DecodeBufs d;
+        bool valid = false;
+        PathResult res;
+    } bp, kb;
+    // The sampler (wfsa_dev_sample_paths; sample.hpp): what the forward pass
+    // keeps beside the decoders' buffers -- the stored rows and log q -- and
+    // its result in kbest_paths_get's layout
+    struct {
+        DecodeBufs d;
+        DevBuf<double> hist, logq;
+        bool valid = false;
+        PathResult res;
+    } sp;
+    // Posterior expected counts (wfsa_dev_posterior_counts; posterior.hpp): the
+    // stored rows, the fixed-point gamma and count rows, log q, entropy, the
+    // cursor and the rows as the waves left them -- and its result, rows in
+    // string order
+    struct {
+        DecodeBufs d;
+        DevBuf<double> hist, logq, ent, val;
+        DevBuf<unsigned long long> gamma, count, cursor;
+        DevBuf<int64_t> start;
+        DevBuf<int32_t> len, idx;
+        bool valid = false;
+        RowResult res;
+    } pc;
     // Per-byte state posteriors and the MEA decode (wfsa_dev_byte_marginals;
-    // marginals.hpp): a fifth buffer set, plus the stored rows, the gamma rows,
-    // the model's grouping tables, the corpus' base offsets, the dense state sums
-    // and what the kernels report -- and its last result for _get
-    DecodeBufs bm;
-    wfsa::MarginalTables bm_tab;        // host copy: g_ptr / g_state turn a group into a state id
-    DevBuf<int32_t> bm_ord, bm_seg, bm_grp;
-    DevBuf<int64_t> bm_base;            // [total_sym + 1], valid while bm_base_ok
-    bool bm_base_ok = false;            // computed for the loaded model and corpus
-    int64_t bm_words = 0;               // state-sum words of the loaded corpus (bm_base's last entry)
-    DevBuf<double> bm_hist, bm_logq, bm_bound, bm_score;
-    DevBuf<unsigned long long> bm_gamma, bm_mass;
-    bool bm_has_path = false;           // the last call decoded
-    std::vector<int64_t> bm_mrow, bm_prow;
-    std::vector<int32_t> bm_midx, bm_pidx;
-    std::vector<double> bm_mval;
-    std::vector<int64_t> bp_prow;
-    std::vector<int32_t> bp_pidx;
-    // the dense path's Viterbi decode (wfsa_dev_dense_best_paths): its last
-    // result for _get, in best_paths_get's layout, and its four timing events
-    bool dbp_valid = false;
-    std::vector<int64_t> dbp_prow;
-    std::vector<int32_t> dbp_pidx;
-    hipEvent_t dbp_ev[4] = {};
-    // the dense path's sampler (wfsa_dev_dense_sample_paths): its last result
-    // for _get, in kbest_paths_get's layout, and its three timing events
-    bool dsp_valid = false;
-    std::vector<int64_t> dsp_srow, dsp_prow;
-    std::vector<double> dsp_logw;
-    std::vector<int32_t> dsp_pidx;
-    hipEvent_t dsp_ev[3] = {};
-    // the dense path's byte marginals and MEA decode
-    // (wfsa_dev_dense_byte_marginals): its last result for _get / _path_get
-    // in byte_marginals' layouts, and its eight timing events
-    bool dbm_valid = false, dbm_has_rows = false, dbm_has_path = false;
-    std::vector<int64_t> dbm_mrow, dbm_prow;
-    std::vector<int32_t> dbm_midx, dbm_pidx;
-    std::vector<double> dbm_mval;
-    hipEvent_t dbm_ev[8] = {};
+    // marginals.hpp): the stored rows, the gamma rows, the model's grouping
+    // tables, the corpus' base offsets, the dense state sums and what the
+    // kernels report -- and its results: rows per corpus byte, and the MEA
+    // paths in best_paths_get's layout
+    struct {
+        DecodeBufs d;
+        wfsa::MarginalTables tab;        // host copy: g_ptr / g_state turn a group into a state id
+        DevBuf<int32_t> ord, seg, grp;
+        DevBuf<int64_t> base;            // [total_sym + 1], valid while base_ok
+        bool base_ok = false;            // computed for the loaded model and corpus
+        int64_t words = 0;               // state-sum words of the loaded corpus (base's last entry)
+        DevBuf<double> hist, logq, bound, score;
+        DevBuf<unsigned long long> gamma, mass;
+        bool valid = false, has_path = false;   // has_path: the last call decoded
+        RowResult rows;
+        PathResult path;
+    } bm;
     // Unconditional generation (wfsa_dev_generate; generate.hpp): the flattened
     // state graph as wfsa_model_desc gives it (uploaded with the model, on the
     // dense path too), the call's weights and running sums, the per-sample
@@ -546,9 +565,39 @@ struct wfsa_dev {
     std::vector<double> gn_h_logw, gn_h_logp;
     std::vector<int8_t> gn_h_status;
     std::vector<int32_t> gn_h_pidx;
-    std::vector<int64_t> kb_srow, kb_prow;
-    std::vector<double> kb_logw;
-    std::vector<int32_t> kb_pidx;
+    // the dense path's Viterbi decode (wfsa_dev_dense_best_paths): its four
+    // timing events and its result in best_paths_get's layout
+    struct {
+        hipEvent_t ev[4] = {};
+        bool valid = false;
+        PathResult res;
+    } dbp;
+    // the dense path's sampler (wfsa_dev_dense_sample_paths): its three timing
+    // events and its result in kbest_paths_get's layout
+    struct {
+        hipEvent_t ev[3] = {};
+        bool valid = false;
+        PathResult res;
+    } dsp;
+    // the dense path's byte marginals and MEA decode
+    // (wfsa_dev_dense_byte_marginals): its eight timing events and its results
+    // in byte_marginals' layouts
+    struct {
+        hipEvent_t ev[8] = {};
+        bool valid = false, has_rows = false, has_path = false;   // has_*: the last call's rows / decode
+        RowResult rows;
+        PathResult path;
+    } dbm;
+    // every feature's "result held" flag and every feature's events, for
+    // invalidate_decodes and wfsa_dev_destroy: a new feature joins both lists
+    bool* const held[9] = {&bp.valid, &kb.valid, &sp.valid, &pc.valid, &bm.valid, &gn_valid, &dbp.valid, &dsp.valid, &dbm.valid};
+    struct EventRun {
+        hipEvent_t* ev;
+        size_t n;
+        template <size_t N>
+        EventRun(hipEvent_t (&e)[N]) : ev(e), n(N) {}
+    };
+    const EventRun events[9] = {bp.d.ev, kb.d.ev, sp.d.ev, pc.d.ev, bm.d.ev, gn_ev, dbp.ev, dsp.ev, dbm.ev};
 
     // communicator
     std::unique_ptr<wfsa::Collective> comm;
@@ -3280,12 +3329,8 @@ void drop_graph(wfsa_dev* ctx) {
 
 // a load ends the decode results held for _get
 void invalidate_decodes(wfsa_dev* ctx) {
-    ctx->bp.valid = ctx->kb.valid = ctx->sp.valid = ctx->pc.valid = ctx->bm.valid = false;
-    ctx->gn_valid = false;
-    ctx->dbp_valid = false;
-    ctx->dsp_valid = false;
-    ctx->dbm_valid = false;
-    ctx->bm_base_ok = false;  // (the state sums' addresses belong to one model and one corpus)
+    for (bool* valid : ctx->held) *valid = false;
+    ctx->bm.base_ok = false;  // (the state sums' addresses belong to one model and one corpus)
 }
 
 // weights in / results out, sized by n_params
@@ -3479,17 +3524,9 @@ void wfsa_dev_destroy(wfsa_dev* ctx) {
     if (ctx->flag) (void)hipHostFree(ctx->flag);
     for (hipEvent_t ev : {ctx->ev0, ctx->ev1})
         if (ev) (void)hipEventDestroy(ev);
-    for (DecodeBufs* d : {&ctx->bp, &ctx->kb, &ctx->sp, &ctx->pc, &ctx->bm})
-        for (hipEvent_t ev : {d->ev0, d->ev1})
-            if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : ctx->gn_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : ctx->dbp_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : ctx->dsp_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : ctx->dbm_ev)
-        if (ev) (void)hipEventDestroy(ev);
+    for (const wfsa_dev::EventRun& r : ctx->events)
+        for (size_t i = 0; i < r.n; ++i)
+            if (r.ev[i]) (void)hipEventDestroy(r.ev[i]);
     for (int i = 0; i < kQnDepth; ++i)
         for (hipEvent_t ev : {ctx->k0[i], ctx->kc[i], ctx->k2[i]})
             if (ev) (void)hipEventDestroy(ev);
@@ -3589,11 +3626,11 @@ int wfsa_dev_load_model(wfsa_dev* ctx, const wfsa_model_desc* model) {
         for (int c = 0; c < 256; ++c) ctx->max_dst = std::max(ctx->max_dst, cptr[size_t(c) + 1] - cptr[size_t(c)]);
         ctx->n_in_edges = int64_t(esrc.size());
         {   // byte_marginals: every byte's destination slots grouped by owner state
-            ctx->bm_tab = wfsa::build_marginal_tables(cptr, dst, tm.owner);
-            const wfsa::MarginalTables& mt = ctx->bm_tab;
-            HIP_TRY(ctx->bm_ord.upload(mt.ord.data(), mt.ord.size(), s));
-            HIP_TRY(ctx->bm_seg.upload(mt.seg.data(), mt.seg.size(), s));
-            HIP_TRY(ctx->bm_grp.upload(mt.grp.data(), mt.grp.size(), s));
+            ctx->bm.tab = wfsa::build_marginal_tables(cptr, dst, tm.owner);
+            const wfsa::MarginalTables& mt = ctx->bm.tab;
+            HIP_TRY(ctx->bm.ord.upload(mt.ord.data(), mt.ord.size(), s));
+            HIP_TRY(ctx->bm.seg.upload(mt.seg.data(), mt.seg.size(), s));
+            HIP_TRY(ctx->bm.grp.upload(mt.grp.data(), mt.grp.size(), s));
         }
         if (dst.empty()) dst.push_back(0);
         if (esrc.empty()) { esrc.push_back(0); eg.push_back(0); }
@@ -4845,59 +4882,83 @@ int wfsa_dev_get_stats(wfsa_dev* ctx, wfsa_dev_stats* out) {
     return WFSA_OK;
 }
 
+}  // extern "C"
 
-// The host side of both decodes (decode.hpp).  The waves in flight come from a
-// scratch budget of 1 GiB (two score rows and the back-pointers per wave, at
-// list length k), at most 16 per CU and never more than there are strings --
-// the corpus does not size it.  `kbest` picks the K-best kernels (also at
-// k = 1) and the checks that belong to them; `name` prefixes every message.
-// Hands back the device's raw results, in DecodeArgs' layout: best[S][k],
-// path and the strings' offsets off[S + 1]; the kernels' time goes to *ms_out.
-// The checks run in the order each entry point always had them, which is why
-// the K-best ones sit here behind `kbest` and not in front of the call.
-static int decode_run(wfsa_dev* ctx, DecodeBufs& d, const char* name, const double* w_full, int32_t k, bool kbest, double* ms_out,
-                      std::vector<double>& best, std::vector<int32_t>& path, std::vector<int64_t>& off) {
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to decode over", name);
+// The per-string features: the decodes, the samplers, the posterior counts and
+// the byte marginals, on the trellis tiers and on the dense path.  What their
+// host sides share is here; every entry point runs its checks in the order
+// check_ctx, check_loaded, its own arguments, check_tier_weights, and only then
+// gives up the result it holds.
+namespace {
+
+// a model and a corpus to walk, and nothing in flight; `verb` says what the
+// entry point would do to the automaton that matrix-file mode lacks
+int check_loaded(wfsa_dev* ctx, const char* name, const char* verb) {
+    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to %s", name, verb);
     if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
     if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
-    if (kbest && (k < 1 || k > WFSA_KBEST_MAX)) return fail(WFSA_ERR_ARG, "%s: k = %d is outside 1 .. %d", name, int(k), WFSA_KBEST_MAX);
-    if (ctx->dense)
-        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to decode it", name);
+    return WFSA_OK;
+}
+
+// The model on the tier this entry point serves, then the weights.  A dense
+// entry point names its trellis `sibling` (null: a trellis entry point); `what`
+// is what the caller wanted done.  The dense passes may meet -inf but no other
+// non-finite value.
+int check_tier_weights(wfsa_dev* ctx, const char* name, const char* sibling, const char* what, const double* w_full) {
+    if (!sibling && ctx->dense)
+        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to %s", name, what);
+    if (sibling && !ctx->dense) return fail(WFSA_ERR_ARG, "%s: the model is not on the dense path; %s with wfsa_dev_%s", name, what, sibling);
     const int32_t np = ctx->n_params;
     if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    d.valid = false;
-    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
-    if (kbest && (ctx->n_in_edges >= wfsa::kKBestMaxEdges || X >= wfsa::kKBestMaxEdges))
-        return fail(WFSA_ERR_CAPACITY, "%s: %lld in-edges / %lld end edges do not fit a packed back-pointer (limit %lld)", name,
-                    (long long)ctx->n_in_edges, (long long)X, (long long)wfsa::kKBestMaxEdges);
-    const int64_t wave_bytes = wfsa::decode_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst, k);
-    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
-    if (fit < 1) {
-        char with_k[32] = "";
-        if (kbest) std::snprintf(with_k, sizeof with_k, ", k = %d", int(k));
-        return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations%s) exceeds the budget", name,
-                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst, with_k);
-    }
-    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
-    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({16 * int64_t(ctx->n_cu), fit, S}));
-    const int grid = int(std::max<int64_t>(1, waves / wpb));
-    const int64_t n_waves = int64_t(grid) * wpb;
-    hipStream_t s = ctx->stream;
-    if (!d.ev0) {
-        HIP_TRY(hipEventCreate(&d.ev0));
-        HIP_TRY(hipEventCreate(&d.ev1));
-    }
-    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
+    for (int32_t j = 0; sibling && j < np; ++j)
+        if (std::isnan(w_full[j]) || w_full[j] == INFINITY) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
+    return WFSA_OK;
+}
+
+// The waves in flight of a wave-per-string walker: as many as a scratch budget
+// of 1 GiB holds at wave_bytes each, at most 16 per CU (or what the environment
+// variable `cap_env` says, if less) and never more than there are strings -- the
+// corpus does not size them.  fit < 1: one string's scratch exceeds the budget,
+// and the caller says so.
+struct WavePlan {
+    int64_t fit = 0;
+    int wpb = 0, grid = 0;
+    int64_t n_waves = 0;
+};
+
+WavePlan wave_plan(const wfsa_dev* ctx, int64_t wave_bytes, const char* cap_env = nullptr) {
+    WavePlan p;
+    p.fit = (int64_t(1) << 30) / wave_bytes;
+    if (p.fit < 1) return p;
+    p.wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, p.fit));
+    int64_t max_waves = 16 * int64_t(ctx->n_cu);
+    if (const char* e = cap_env ? std::getenv(cap_env) : nullptr) max_waves = std::max<int64_t>(1, std::min<int64_t>(max_waves, std::atoll(e)));
+    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({max_waves, p.fit, ctx->n_strings}));
+    p.grid = int(std::max<int64_t>(1, waves / p.wpb));
+    p.n_waves = int64_t(p.grid) * p.wpb;
+    return p;
+}
+
+template <size_t N>
+int ensure_events(hipEvent_t (&evs)[N]) {
+    for (hipEvent_t& ev : evs)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    return WFSA_OK;
+}
+
+// the call's weights into d.w, the zero slot last
+int upload_weights(wfsa_dev* ctx, DecodeBufs& d, const double* w_full) {
+    const int32_t np = ctx->n_params;
+    std::vector<double>& hw = d.hw;
+    hw.assign(size_t(np) + 1, 0.0);
     if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
-    const size_t n_path = size_t(ctx->total_sym + S) * size_t(k);
-    const size_t n_best = size_t(S) * size_t(k);
-    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
-    HIP_TRY(d.lw.alloc(size_t(E + X)));
-    HIP_TRY(d.score.alloc(size_t(n_waves * wfsa::decode_score_doubles(ctx->n_nodes, k))));
-    HIP_TRY(d.back.alloc(size_t(n_waves * wfsa::decode_back_ints(ctx->max_len, ctx->max_dst, k))));
-    HIP_TRY(d.ctr.alloc(1));
-    HIP_TRY(d.best.alloc(n_best));
-    HIP_TRY(d.path.alloc(n_path));
+    HIP_TRY(d.w.upload(hw.data(), hw.size(), ctx->stream));
+    return WFSA_OK;
+}
+
+// DecodeArgs' view of the loaded model and corpus and of d's weights, edge
+// log-weights, scores and work counter; k, back, best and path are the caller's
+wfsa::DecodeArgs decode_args(const wfsa_dev* ctx, const DecodeBufs& d) {
     wfsa::DecodeArgs a{};
     a.w.c_ptr = ctx->w_cptr.ptr;
     a.w.dst = ctx->w_dst.ptr;
@@ -4909,24 +4970,71 @@ static int decode_run(wfsa_dev* ctx, DecodeBufs& d, const char* name, const doub
     a.pidx = ctx->pidx.ptr;
     a.n_nodes = ctx->n_nodes;
     a.start = ctx->start;
-    a.n_edges = int32_t(E);
-    a.n_end = int32_t(X);
+    a.n_edges = int32_t(ctx->n_edges);
+    a.n_end = int32_t(ctx->n_end);
     a.sym = ctx->sym.ptr;
     a.off = ctx->off.ptr;
-    a.n_strings = int32_t(S);
+    a.n_strings = int32_t(ctx->n_strings);
     a.max_len = ctx->max_len;
     a.max_dst = ctx->max_dst;
-    a.k = k;
     a.wt = d.w.ptr;
     a.lw = d.lw.ptr;
     a.score = d.score.ptr;
-    a.back = d.back.ptr;
     a.ctr = d.ctr.ptr;
+    return a;
+}
+
+// what a _get says when `feature` has left no result, or left none of this kind
+int no_result(const char* feature, const char* get) {
+    return fail(WFSA_ERR_ARG, "%s%s: no wfsa_dev_%s result since the last load", feature, get, feature);
+}
+
+int asked_for_none(const char* feature, const char* get, const char* arg) {
+    return fail(WFSA_ERR_ARG, "%s%s: the last wfsa_dev_%s call had %s = 0", feature, get, feature, arg);
+}
+
+// The device side of both decodes (decode.hpp), after check_loaded: two score
+// rows and the back-pointers per wave, at list length k.  `kbest` picks the
+// K-best kernels (also at k = 1) and their capacity check; `name` prefixes every
+// message.  Hands back the device's raw results, in DecodeArgs' layout:
+// best[S][k], path and the strings' offsets off[S + 1]; the kernels' time goes
+// to *ms_out.
+int decode_run(wfsa_dev* ctx, wfsa_dev::DecodePaths& f, const char* name, const double* w_full, int32_t k, bool kbest, double* ms_out,
+               std::vector<double>& best, std::vector<int32_t>& path, std::vector<int64_t>& off) {
+    if (int rc = check_tier_weights(ctx, name, nullptr, "decode it", w_full)) return rc;
+    DecodeBufs& d = f.d;
+    f.valid = false;
+    const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
+    if (kbest && (ctx->n_in_edges >= wfsa::kKBestMaxEdges || X >= wfsa::kKBestMaxEdges))
+        return fail(WFSA_ERR_CAPACITY, "%s: %lld in-edges / %lld end edges do not fit a packed back-pointer (limit %lld)", name,
+                    (long long)ctx->n_in_edges, (long long)X, (long long)wfsa::kKBestMaxEdges);
+    const int64_t wave_bytes = wfsa::decode_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst, k);
+    const WavePlan wp = wave_plan(ctx, wave_bytes);
+    if (wp.fit < 1) {
+        char with_k[32] = "";
+        if (kbest) std::snprintf(with_k, sizeof with_k, ", k = %d", int(k));
+        return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations%s) exceeds the budget", name,
+                    (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst, with_k);
+    }
+    hipStream_t s = ctx->stream;
+    if (int rc = ensure_events(d.ev)) return rc;
+    const size_t n_path = size_t(ctx->total_sym + S) * size_t(k);
+    const size_t n_best = size_t(S) * size_t(k);
+    if (int rc = upload_weights(ctx, d, w_full)) return rc;
+    HIP_TRY(d.lw.alloc(size_t(E + X)));
+    HIP_TRY(d.score.alloc(size_t(wp.n_waves * wfsa::decode_score_doubles(ctx->n_nodes, k))));
+    HIP_TRY(d.back.alloc(size_t(wp.n_waves * wfsa::decode_back_ints(ctx->max_len, ctx->max_dst, k))));
+    HIP_TRY(d.ctr.alloc(1));
+    HIP_TRY(d.best.alloc(n_best));
+    HIP_TRY(d.path.alloc(n_path));
+    wfsa::DecodeArgs a = decode_args(ctx, d);
+    a.k = k;
+    a.back = d.back.ptr;
     a.best = d.best.ptr;
     a.path = d.path.ptr;
-    HIP_TRY(hipEventRecord(d.ev0, s));
-    HIP_TRY(kbest ? wfsa::launch_kbest_paths(a, grid, wpb, s) : wfsa::launch_best_paths(a, grid, wpb, s));
-    HIP_TRY(hipEventRecord(d.ev1, s));
+    HIP_TRY(hipEventRecord(d.ev[0], s));
+    HIP_TRY(kbest ? wfsa::launch_kbest_paths(a, wp.grid, wp.wpb, s) : wfsa::launch_best_paths(a, wp.grid, wp.wpb, s));
+    HIP_TRY(hipEventRecord(d.ev[1], s));
     path.resize(n_path);
     best.resize(n_best);
     off.resize(size_t(S) + 1);
@@ -4935,7 +5043,7 @@ static int decode_run(wfsa_dev* ctx, DecodeBufs& d, const char* name, const doub
     HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
     *ms_out = double(ms);
     return WFSA_OK;
 }
@@ -4943,8 +5051,7 @@ static int decode_run(wfsa_dev* ctx, DecodeBufs& d, const char* name, const doub
 // One path as Fsa parameters: the parameter lists of its L + 1 combined edge
 // ids (h_pptr / h_pidx), in path order, appended to pidx.  The first L are
 // byte-consuming edges and the last is an end edge; `rank` < 0: a Viterbi path.
-static int expand_path(wfsa_dev* ctx, const char* name, int64_t string, int rank, const int32_t* pe, int64_t L,
-                       std::vector<int32_t>& pidx) {
+int expand_path(wfsa_dev* ctx, const char* name, int64_t string, int rank, const int32_t* pe, int64_t L, std::vector<int32_t>& pidx) {
     const int64_t E = ctx->n_edges, X = ctx->n_end;
     for (int64_t t = 0; t <= L; ++t) {
         const int64_t g = pe[t];
@@ -4955,38 +5062,64 @@ static int expand_path(wfsa_dev* ctx, const char* name, int64_t string, int rank
             return fail(WFSA_ERR_HIP, "%s: string %lld, path %d: edge %lld at step %lld is not a path edge", name, (long long)string, rank,
                         (long long)g, (long long)t);
         }
-        pidx.insert(pidx.end(), ctx->h_pidx.begin() + ctx->h_pptr[size_t(g)], ctx->h_pidx.begin() + ctx->h_pptr[size_t(g) + 1]);
+        // push_back and not the range insert this had before the entry points shared their prologue: in their new
+        // shape the compiler no longer inlined that insert into kbest_paths but called it once per edge, 6 % of the
+        // call's host time at 100 000 strings.  An edge's list is short, and push_back is inline wherever this runs.
+        for (int32_t q = ctx->h_pptr[size_t(g)]; q < ctx->h_pptr[size_t(g) + 1]; ++q) pidx.push_back(ctx->h_pidx[size_t(q)]);
     }
     return WFSA_OK;
 }
 
+// ... and one path of the dense path: of its 2 (L + 1) parameter codes, those
+// that are Fsa parameter ids (>= 0; the others mark an edge without one), in
+// path order, appended to pidx; `sample` < 0: a Viterbi or MEA path
+int expand_codes(wfsa_dev* ctx, const char* name, int64_t string, int sample, const int32_t* cd, int64_t L, std::vector<int32_t>& pidx) {
+    for (int64_t q = 0; q < 2 * (L + 1); ++q) {
+        if (cd[q] == wfsa::kCodeNone || cd[q] >= ctx->n_params) {
+            if (sample < 0)
+                return fail(WFSA_ERR_HIP, "%s: string %lld: code %d at entry %lld is not a path edge", name, (long long)string, int(cd[q]),
+                            (long long)q);
+            return fail(WFSA_ERR_HIP, "%s: string %lld, sample %d: code %d at entry %lld is not a path edge", name, (long long)string, sample,
+                        int(cd[q]), (long long)q);
+        }
+        if (cd[q] >= 0) pidx.push_back(cd[q]);
+    }
+    return WFSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 // Viterbi decode: the scalar kernel at k = 1
 int wfsa_dev_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries) {
+    const char* name = "best_paths";
     std::vector<double> best;
     std::vector<int32_t> path;
     std::vector<int64_t> off;
     if (int rc = check_ctx(ctx)) return rc;
-    if (int rc = decode_run(ctx, ctx->bp, "best_paths", w_full, 1, false, &ctx->stats.best_path_ms, best, path, off)) return rc;
+    if (int rc = check_loaded(ctx, name, "decode over")) return rc;
+    PathResult& res = ctx->bp.res;
+    if (int rc = decode_run(ctx, ctx->bp, name, w_full, 1, false, &ctx->stats.best_path_ms, best, path, off)) return rc;
     const int64_t S = ctx->n_strings;
     if (best_logw && S > 0) std::memcpy(best_logw, best.data(), size_t(S) * sizeof(double));
-    ctx->bp_prow.assign(size_t(S) + 1, 0);
-    ctx->bp_pidx.clear();
+    res.prow.assign(size_t(S) + 1, 0);
+    res.pidx.clear();
     for (int64_t i = 0; i < S; ++i) {
         const int32_t* pe = path.data() + off[i] + i;
         if (pe[0] >= 0)
-            if (int rc = expand_path(ctx, "best_paths", i, -1, pe, off[i + 1] - off[i], ctx->bp_pidx)) return rc;
-        ctx->bp_prow[size_t(i) + 1] = int64_t(ctx->bp_pidx.size());
+            if (int rc = expand_path(ctx, name, i, -1, pe, off[i + 1] - off[i], res.pidx)) return rc;
+        res.prow[size_t(i) + 1] = int64_t(res.pidx.size());
     }
     ctx->bp.valid = true;
-    if (n_entries) *n_entries = int64_t(ctx->bp_pidx.size());
+    if (n_entries) *n_entries = int64_t(res.pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->bp.valid) return fail(WFSA_ERR_ARG, "best_paths_get: no wfsa_dev_best_paths result since the last load");
-    if (prow) std::memcpy(prow, ctx->bp_prow.data(), ctx->bp_prow.size() * sizeof(int64_t));
-    if (pidx && !ctx->bp_pidx.empty()) std::memcpy(pidx, ctx->bp_pidx.data(), ctx->bp_pidx.size() * sizeof(int32_t));
+    if (!ctx->bp.valid) return no_result("best_paths", "_get");
+    ctx->bp.res.copy_out(nullptr, nullptr, prow, pidx);
     return WFSA_OK;
 }
 
@@ -4996,20 +5129,13 @@ int wfsa_dev_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
 int wfsa_dev_dense_best_paths(wfsa_dev* ctx, const double* w_full, double* best_logw, int64_t* n_entries) {
     const char* name = "dense_best_paths";
     if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to decode over", name);
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
-    if (!ctx->dense)
-        return fail(WFSA_ERR_ARG, "%s: the model is not on the dense path; decode it with wfsa_dev_best_paths", name);
-    const int32_t np = ctx->n_params;
-    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    for (int32_t j = 0; j < np; ++j)   // (-inf is the only non-finite value the pass may meet)
-        if (std::isnan(w_full[j]) || w_full[j] == INFINITY) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
-    ctx->dbp_valid = false;
+    if (int rc = check_loaded(ctx, name, "decode over")) return rc;
+    if (int rc = check_tier_weights(ctx, name, "best_paths", "decode it", w_full)) return rc;
+    auto& f = ctx->dbp;
+    f.valid = false;
     hipStream_t s = ctx->stream;
-    for (hipEvent_t& ev : ctx->dbp_ev)
-        if (!ev) HIP_TRY(hipEventCreate(&ev));
-    const hipError_t e = ctx->dense->enqueue_best_paths(w_full, ctx->dbp_ev, s);
+    if (int rc = ensure_events(f.ev)) return rc;
+    const hipError_t e = ctx->dense->enqueue_best_paths(w_full, f.ev, s);
     if (e == hipErrorOutOfMemory)
         return fail(WFSA_ERR_CAPACITY, "%s: the score history of %lld bytes (%d steps x %d row slots x %d states) cannot be allocated", name,
                     (long long)ctx->dense->best_paths_history_bytes(), ctx->dense->steps(), ctx->dense->rows(), ctx->dense->np());
@@ -5021,37 +5147,29 @@ int wfsa_dev_dense_best_paths(wfsa_dev* ctx, const double* w_full, double* best_
     HIP_TRY(ctx->dense->best_paths_download(logw.data(), codes.data(), s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms[3] = {0.f, 0.f, 0.f};
-    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ctx->dbp_ev[i], ctx->dbp_ev[i + 1]));
+    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], f.ev[i], f.ev[i + 1]));
     ctx->stats.dense_bp_tables_ms = double(ms[0]);
     ctx->stats.dense_bp_forward_ms = double(ms[1]);
     ctx->stats.dense_bp_backtrack_ms = double(ms[2]);
     ctx->stats.best_path_ms = double(ms[0]) + double(ms[1]) + double(ms[2]);
-    ctx->dbp_prow.assign(size_t(S) + 1, 0);
-    ctx->dbp_pidx.clear();
+    f.res.prow.assign(size_t(S) + 1, 0);
+    f.res.pidx.clear();
     for (int64_t i = 0; i < S; ++i) {
-        if (logw[size_t(i)] > -INFINITY) {
-            const int32_t* cd = codes.data() + 2 * (off[size_t(i)] + i);
-            const int64_t n = 2 * (off[size_t(i) + 1] - off[size_t(i)] + 1);
-            for (int64_t q = 0; q < n; ++q) {
-                if (cd[q] == wfsa::kCodeNone || cd[q] >= np)
-                    return fail(WFSA_ERR_HIP, "%s: string %lld: code %d at entry %lld is not a path edge", name, (long long)i, int(cd[q]),
-                                (long long)q);
-                if (cd[q] >= 0) ctx->dbp_pidx.push_back(cd[q]);
-            }
-        }
-        ctx->dbp_prow[size_t(i) + 1] = int64_t(ctx->dbp_pidx.size());
+        if (logw[size_t(i)] > -INFINITY)
+            if (int rc = expand_codes(ctx, name, i, -1, codes.data() + 2 * (off[size_t(i)] + i), off[size_t(i) + 1] - off[size_t(i)], f.res.pidx))
+                return rc;
+        f.res.prow[size_t(i) + 1] = int64_t(f.res.pidx.size());
     }
     if (best_logw && S > 0) std::memcpy(best_logw, logw.data(), size_t(S) * sizeof(double));
-    ctx->dbp_valid = true;
-    if (n_entries) *n_entries = int64_t(ctx->dbp_pidx.size());
+    f.valid = true;
+    if (n_entries) *n_entries = int64_t(f.res.pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_dense_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->dbp_valid) return fail(WFSA_ERR_ARG, "dense_best_paths_get: no wfsa_dev_dense_best_paths result since the last load");
-    if (prow) std::memcpy(prow, ctx->dbp_prow.data(), ctx->dbp_prow.size() * sizeof(int64_t));
-    if (pidx && !ctx->dbp_pidx.empty()) std::memcpy(pidx, ctx->dbp_pidx.data(), ctx->dbp_pidx.size() * sizeof(int32_t));
+    if (!ctx->dbp.valid) return no_result("dense_best_paths", "_get");
+    ctx->dbp.res.copy_out(nullptr, nullptr, prow, pidx);
     return WFSA_OK;
 }
 
@@ -5059,41 +5177,42 @@ int wfsa_dev_dense_best_paths_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
 // weights come first, descending.
 int wfsa_dev_kbest_paths(wfsa_dev* ctx, const double* w_full, int32_t k, int64_t* n_paths, int64_t* n_entries) {
     static_assert(WFSA_KBEST_MAX == wfsa::kKBestMax, "the header's limit is the kernel's largest capacity");
+    const char* name = "kbest_paths";
     std::vector<double> best;
     std::vector<int32_t> path;
     std::vector<int64_t> off;
     if (int rc = check_ctx(ctx)) return rc;
-    if (int rc = decode_run(ctx, ctx->kb, "kbest_paths", w_full, k, true, &ctx->stats.kbest_path_ms, best, path, off)) return rc;
+    if (int rc = check_loaded(ctx, name, "decode over")) return rc;
+    if (k < 1 || k > WFSA_KBEST_MAX) return fail(WFSA_ERR_ARG, "%s: k = %d is outside 1 .. %d", name, int(k), WFSA_KBEST_MAX);
+    PathResult& res = ctx->kb.res;
+    if (int rc = decode_run(ctx, ctx->kb, name, w_full, k, true, &ctx->stats.kbest_path_ms, best, path, off)) return rc;
     const int64_t S = ctx->n_strings;
-    ctx->kb_srow.assign(size_t(S) + 1, 0);
-    ctx->kb_prow.assign(1, 0);
-    ctx->kb_logw.clear();
-    ctx->kb_pidx.clear();
+    res.srow.assign(size_t(S) + 1, 0);
+    res.prow.assign(1, 0);
+    res.logw.clear();
+    res.pidx.clear();
     for (int64_t i = 0; i < S; ++i) {
         const int64_t L = off[i + 1] - off[i];
         const int32_t* ps = path.data() + (off[i] + i) * int64_t(k);
         for (int32_t t = 0; t < k; ++t) {
             const double v = best[size_t(i) * size_t(k) + size_t(t)];
             if (!(v > -INFINITY)) break;
-            if (int rc = expand_path(ctx, "kbest_paths", i, int(t), ps + int64_t(t) * (L + 1), L, ctx->kb_pidx)) return rc;
-            ctx->kb_logw.push_back(v);
-            ctx->kb_prow.push_back(int64_t(ctx->kb_pidx.size()));
+            if (int rc = expand_path(ctx, name, i, int(t), ps + int64_t(t) * (L + 1), L, res.pidx)) return rc;
+            res.logw.push_back(v);
+            res.prow.push_back(int64_t(res.pidx.size()));
         }
-        ctx->kb_srow[size_t(i) + 1] = int64_t(ctx->kb_logw.size());
+        res.srow[size_t(i) + 1] = int64_t(res.logw.size());
     }
     ctx->kb.valid = true;
-    if (n_paths) *n_paths = int64_t(ctx->kb_logw.size());
-    if (n_entries) *n_entries = int64_t(ctx->kb_pidx.size());
+    if (n_paths) *n_paths = int64_t(res.logw.size());
+    if (n_entries) *n_entries = int64_t(res.pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_kbest_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->kb.valid) return fail(WFSA_ERR_ARG, "kbest_paths_get: no wfsa_dev_kbest_paths result since the last load");
-    if (srow) std::memcpy(srow, ctx->kb_srow.data(), ctx->kb_srow.size() * sizeof(int64_t));
-    if (logw && !ctx->kb_logw.empty()) std::memcpy(logw, ctx->kb_logw.data(), ctx->kb_logw.size() * sizeof(double));
-    if (prow) std::memcpy(prow, ctx->kb_prow.data(), ctx->kb_prow.size() * sizeof(int64_t));
-    if (pidx && !ctx->kb_pidx.empty()) std::memcpy(pidx, ctx->kb_pidx.data(), ctx->kb_pidx.size() * sizeof(int32_t));
+    if (!ctx->kb.valid) return no_result("kbest_paths", "_get");
+    ctx->kb.res.copy_out(srow, logw, prow, pidx);
     return WFSA_OK;
 }
 
@@ -5105,90 +5224,57 @@ int wfsa_dev_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, uint64
     static_assert(WFSA_SAMPLE_MAX == wfsa::kSampleMax, "the header's limit is one walking lane per sample");
     const char* name = "sample_paths";
     if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to sample over", name);
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (int rc = check_loaded(ctx, name, "sample over")) return rc;
     if (n < 1 || n > WFSA_SAMPLE_MAX) return fail(WFSA_ERR_ARG, "%s: n = %d is outside 1 .. %d", name, int(n), WFSA_SAMPLE_MAX);
-    if (ctx->dense)
-        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to sample it", name);
-    const int32_t np = ctx->n_params;
-    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    DecodeBufs& d = ctx->sp;
-    d.valid = false;
+    if (int rc = check_tier_weights(ctx, name, nullptr, "sample it", w_full)) return rc;
+    auto& f = ctx->sp;
+    DecodeBufs& d = f.d;
+    f.valid = false;
     const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
     const int64_t wave_bytes = wfsa::sample_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst);
-    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
-    if (fit < 1)
+    const WavePlan wp = wave_plan(ctx, wave_bytes);
+    if (wp.fit < 1)
         return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations) exceeds the budget", name,
                     (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst);
-    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
-    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({16 * int64_t(ctx->n_cu), fit, S}));
-    const int grid = int(std::max<int64_t>(1, waves / wpb));
-    const int64_t n_waves = int64_t(grid) * wpb;
     hipStream_t s = ctx->stream;
-    if (!d.ev0) {
-        HIP_TRY(hipEventCreate(&d.ev0));
-        HIP_TRY(hipEventCreate(&d.ev1));
-    }
-    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
-    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    if (int rc = ensure_events(d.ev)) return rc;
     const size_t n_path = size_t(ctx->total_sym + S) * size_t(n);
     const size_t n_best = size_t(S) * size_t(n);
-    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
+    if (int rc = upload_weights(ctx, d, w_full)) return rc;
     HIP_TRY(d.lw.alloc(size_t(E + X)));
-    HIP_TRY(d.score.alloc(size_t(n_waves * wfsa::sample_score_doubles(ctx->n_nodes))));
-    HIP_TRY(ctx->sp_hist.alloc(size_t(n_waves * wfsa::sample_hist_doubles(ctx->max_len, ctx->max_dst))));
+    HIP_TRY(d.score.alloc(size_t(wp.n_waves * wfsa::sample_score_doubles(ctx->n_nodes))));
+    HIP_TRY(f.hist.alloc(size_t(wp.n_waves * wfsa::sample_hist_doubles(ctx->max_len, ctx->max_dst))));
     HIP_TRY(d.ctr.alloc(1));
     HIP_TRY(d.best.alloc(n_best));
     HIP_TRY(d.path.alloc(n_path));
-    HIP_TRY(ctx->sp_logq.alloc(size_t(S)));
+    HIP_TRY(f.logq.alloc(size_t(S)));
     wfsa::SampleArgs a{};
-    a.d.w.c_ptr = ctx->w_cptr.ptr;
-    a.d.w.dst = ctx->w_dst.ptr;
-    a.d.w.e_ptr = ctx->w_eptr.ptr;
-    a.d.w.e_src = ctx->w_esrc.ptr;
-    a.d.w.e_g = ctx->w_eg.ptr;
-    a.d.x_ptr = ctx->x_ptr.ptr;
-    a.d.pptr = ctx->pptr.ptr;
-    a.d.pidx = ctx->pidx.ptr;
-    a.d.n_nodes = ctx->n_nodes;
-    a.d.start = ctx->start;
-    a.d.n_edges = int32_t(E);
-    a.d.n_end = int32_t(X);
-    a.d.sym = ctx->sym.ptr;
-    a.d.off = ctx->off.ptr;
-    a.d.n_strings = int32_t(S);
-    a.d.max_len = ctx->max_len;
-    a.d.max_dst = ctx->max_dst;
-    a.d.k = n;
-    a.d.wt = d.w.ptr;
-    a.d.lw = d.lw.ptr;
-    a.d.score = d.score.ptr;
-    a.d.back = nullptr;   // (no back-pointers: the rows are kept instead)
-    a.d.ctr = d.ctr.ptr;
+    a.d = decode_args(ctx, d);
+    a.d.k = n;   // (no back-pointers: the rows are kept instead)
     a.d.best = d.best.ptr;
     a.d.path = d.path.ptr;
-    a.hist = ctx->sp_hist.ptr;
-    a.logq = ctx->sp_logq.ptr;
+    a.hist = f.hist.ptr;
+    a.logq = f.logq.ptr;
     a.seed = seed;
-    HIP_TRY(hipEventRecord(d.ev0, s));
-    HIP_TRY(wfsa::launch_sample_paths(a, grid, wpb, s));
-    HIP_TRY(hipEventRecord(d.ev1, s));
+    HIP_TRY(hipEventRecord(d.ev[0], s));
+    HIP_TRY(wfsa::launch_sample_paths(a, wp.grid, wp.wpb, s));
+    HIP_TRY(hipEventRecord(d.ev[1], s));
     std::vector<int32_t> path(n_path);
     std::vector<double> best(n_best), lq(size_t(S), 0.0);
     std::vector<int64_t> off(size_t(S) + 1);
     HIP_TRY(d.best.download(best.data(), n_best, s));
     HIP_TRY(d.path.download(path.data(), n_path, s));
-    HIP_TRY(ctx->sp_logq.download(lq.data(), size_t(S), s));
+    HIP_TRY(f.logq.download(lq.data(), size_t(S), s));
     HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
     ctx->stats.sample_path_ms = double(ms);
-    ctx->sp_srow.assign(size_t(S) + 1, 0);
-    ctx->sp_prow.assign(1, 0);
-    ctx->sp_logw.clear();
-    ctx->sp_pidx.clear();
+    PathResult& res = f.res;
+    res.srow.assign(size_t(S) + 1, 0);
+    res.prow.assign(1, 0);
+    res.logw.clear();
+    res.pidx.clear();
     for (int64_t i = 0; i < S; ++i) {
         const int64_t L = off[i + 1] - off[i];
         const int32_t* ps = path.data() + (off[i] + i) * int64_t(n);
@@ -5197,26 +5283,23 @@ int wfsa_dev_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, uint64
                 const double v = best[size_t(i) * size_t(n) + size_t(t)];
                 if (ps[int64_t(t) * (L + 1)] < 0 || !(v > -INFINITY))
                     return fail(WFSA_ERR_HIP, "%s: string %lld, sample %d: the walk found no edge of positive mass", name, (long long)i, int(t));
-                if (int rc = expand_path(ctx, name, i, int(t), ps + int64_t(t) * (L + 1), L, ctx->sp_pidx)) return rc;
-                ctx->sp_logw.push_back(v);
-                ctx->sp_prow.push_back(int64_t(ctx->sp_pidx.size()));
+                if (int rc = expand_path(ctx, name, i, int(t), ps + int64_t(t) * (L + 1), L, res.pidx)) return rc;
+                res.logw.push_back(v);
+                res.prow.push_back(int64_t(res.pidx.size()));
             }
-        ctx->sp_srow[size_t(i) + 1] = int64_t(ctx->sp_logw.size());
+        res.srow[size_t(i) + 1] = int64_t(res.logw.size());
     }
-    d.valid = true;
+    f.valid = true;
     if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
-    if (n_paths) *n_paths = int64_t(ctx->sp_logw.size());
-    if (n_entries) *n_entries = int64_t(ctx->sp_pidx.size());
+    if (n_paths) *n_paths = int64_t(res.logw.size());
+    if (n_entries) *n_entries = int64_t(res.pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->sp.valid) return fail(WFSA_ERR_ARG, "sample_paths_get: no wfsa_dev_sample_paths result since the last load");
-    if (srow) std::memcpy(srow, ctx->sp_srow.data(), ctx->sp_srow.size() * sizeof(int64_t));
-    if (logw && !ctx->sp_logw.empty()) std::memcpy(logw, ctx->sp_logw.data(), ctx->sp_logw.size() * sizeof(double));
-    if (prow) std::memcpy(prow, ctx->sp_prow.data(), ctx->sp_prow.size() * sizeof(int64_t));
-    if (pidx && !ctx->sp_pidx.empty()) std::memcpy(pidx, ctx->sp_pidx.data(), ctx->sp_pidx.size() * sizeof(int32_t));
+    if (!ctx->sp.valid) return no_result("sample_paths", "_get");
+    ctx->sp.res.copy_out(srow, logw, prow, pidx);
     return WFSA_OK;
 }
 
@@ -5228,25 +5311,19 @@ int wfsa_dev_dense_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, 
                                 int64_t* n_entries) {
     const char* name = "dense_sample_paths";
     if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to sample over", name);
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (int rc = check_loaded(ctx, name, "sample over")) return rc;
     if (n < 1 || n > WFSA_SAMPLE_MAX) return fail(WFSA_ERR_ARG, "%s: n = %d is outside 1 .. %d", name, int(n), WFSA_SAMPLE_MAX);
-    if (!ctx->dense)
-        return fail(WFSA_ERR_ARG, "%s: the model is not on the dense path; sample it with wfsa_dev_sample_paths", name);
-    const int32_t np = ctx->n_params;
-    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    for (int32_t j = 0; j < np; ++j)   // (-inf is the only non-finite value the pass may meet)
-        if (std::isnan(w_full[j]) || w_full[j] == INFINITY) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
+    if (int rc = check_tier_weights(ctx, name, "sample_paths", "sample it", w_full)) return rc;
     const size_t out_bytes = ctx->dense->sample_paths_output_bytes(n);
     if (out_bytes > (size_t(1) << 32))
         return fail(WFSA_ERR_CAPACITY, "%s: the path output of %lld bytes (%d samples x %lld bytes and strings) exceeds 4 GiB", name,
                     (long long)out_bytes, int(n), (long long)(ctx->dense->total_symbols() + ctx->n_strings));
-    ctx->dsp_valid = false;
+    auto& f = ctx->dsp;
+    PathResult& res = f.res;
+    f.valid = false;
     hipStream_t s = ctx->stream;
-    for (hipEvent_t& ev : ctx->dsp_ev)
-        if (!ev) HIP_TRY(hipEventCreate(&ev));
-    const hipError_t e = ctx->dense->enqueue_sample_paths(w_full, n, seed, ctx->dsp_ev, s);
+    if (int rc = ensure_events(f.ev)) return rc;
+    const hipError_t e = ctx->dense->enqueue_sample_paths(w_full, n, seed, f.ev, s);
     if (e == hipErrorOutOfMemory)
         return fail(WFSA_ERR_CAPACITY, "%s: the alpha history of %lld bytes (%d steps x %d row slots x %d states) cannot be allocated", name,
                     (long long)ctx->dense->best_paths_history_bytes(), ctx->dense->steps(), ctx->dense->rows(), ctx->dense->np());
@@ -5258,14 +5335,14 @@ int wfsa_dev_dense_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, 
     HIP_TRY(ctx->dense->sample_paths_download(n, lq.data(), lw.data(), codes.data(), s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms[2] = {0.f, 0.f};
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ctx->dsp_ev[i], ctx->dsp_ev[i + 1]));
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], f.ev[i], f.ev[i + 1]));
     ctx->stats.dense_sp_forward_ms = double(ms[0]);
     ctx->stats.dense_sp_backward_ms = double(ms[1]);
     ctx->stats.sample_path_ms = double(ms[0]) + double(ms[1]);
-    ctx->dsp_srow.assign(size_t(S) + 1, 0);
-    ctx->dsp_prow.assign(1, 0);
-    ctx->dsp_logw.clear();
-    ctx->dsp_pidx.clear();
+    res.srow.assign(size_t(S) + 1, 0);
+    res.prow.assign(1, 0);
+    res.logw.clear();
+    res.pidx.clear();
     for (int64_t i = 0; i < S; ++i) {
         const int64_t L = off[size_t(i) + 1] - off[size_t(i)];
         if (lq[size_t(i)] > -INFINITY)
@@ -5274,32 +5351,23 @@ int wfsa_dev_dense_sample_paths(wfsa_dev* ctx, const double* w_full, int32_t n, 
                 const int32_t* cd = codes.data() + 2 * ((off[size_t(i)] + i) * int64_t(n) + int64_t(t) * (L + 1));
                 if (cd[0] == wfsa::kCodeNone || !(v > -INFINITY))
                     return fail(WFSA_ERR_HIP, "%s: string %lld, sample %d: the walk found no state of positive mass", name, (long long)i, int(t));
-                for (int64_t q = 0; q < 2 * (L + 1); ++q) {
-                    if (cd[q] == wfsa::kCodeNone || cd[q] >= np)
-                        return fail(WFSA_ERR_HIP, "%s: string %lld, sample %d: code %d at entry %lld is not a path edge", name, (long long)i,
-                                    int(t), int(cd[q]), (long long)q);
-                    if (cd[q] >= 0) ctx->dsp_pidx.push_back(cd[q]);
-                }
-                ctx->dsp_logw.push_back(v);
-                ctx->dsp_prow.push_back(int64_t(ctx->dsp_pidx.size()));
+                if (int rc = expand_codes(ctx, name, i, int(t), cd, L, res.pidx)) return rc;
+                res.logw.push_back(v);
+                res.prow.push_back(int64_t(res.pidx.size()));
             }
-        ctx->dsp_srow[size_t(i) + 1] = int64_t(ctx->dsp_logw.size());
+        res.srow[size_t(i) + 1] = int64_t(res.logw.size());
     }
-    ctx->dsp_valid = true;
+    f.valid = true;
     if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
-    if (n_paths) *n_paths = int64_t(ctx->dsp_logw.size());
-    if (n_entries) *n_entries = int64_t(ctx->dsp_pidx.size());
+    if (n_paths) *n_paths = int64_t(res.logw.size());
+    if (n_entries) *n_entries = int64_t(res.pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_dense_sample_paths_get(wfsa_dev* ctx, int64_t* srow, double* logw, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->dsp_valid)
-        return fail(WFSA_ERR_ARG, "dense_sample_paths_get: no wfsa_dev_dense_sample_paths result since the last load");
-    if (srow) std::memcpy(srow, ctx->dsp_srow.data(), ctx->dsp_srow.size() * sizeof(int64_t));
-    if (logw && !ctx->dsp_logw.empty()) std::memcpy(logw, ctx->dsp_logw.data(), ctx->dsp_logw.size() * sizeof(double));
-    if (prow) std::memcpy(prow, ctx->dsp_prow.data(), ctx->dsp_prow.size() * sizeof(int64_t));
-    if (pidx && !ctx->dsp_pidx.empty()) std::memcpy(pidx, ctx->dsp_pidx.data(), ctx->dsp_pidx.size() * sizeof(int32_t));
+    if (!ctx->dsp.valid) return no_result("dense_sample_paths", "_get");
+    ctx->dsp.res.copy_out(srow, logw, prow, pidx);
     return WFSA_OK;
 }
 
@@ -5311,22 +5379,15 @@ int wfsa_dev_dense_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t r
                                   double* path_logw, int64_t* n_entries, int64_t* n_path_entries) {
     const char* name = "dense_byte_marginals";
     if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to walk", name);
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
+    if (int rc = check_loaded(ctx, name, "walk")) return rc;
     if (!rows && !decode) return fail(WFSA_ERR_ARG, "%s: rows = 0 and decode = 0 ask for nothing", name);
-    if (!ctx->dense)
-        return fail(WFSA_ERR_ARG, "%s: the model is not on the dense path; take its marginals with wfsa_dev_byte_marginals", name);
-    const int32_t np = ctx->n_params;
-    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    for (int32_t j = 0; j < np; ++j)   // (-inf is the only non-finite value the pass may meet)
-        if (std::isnan(w_full[j]) || w_full[j] == INFINITY) return fail(WFSA_ERR_ARG, "%s: a weight is NaN or +inf", name);
-    ctx->dbm_valid = false;
+    if (int rc = check_tier_weights(ctx, name, "byte_marginals", "take its marginals", w_full)) return rc;
+    auto& f = ctx->dbm;
+    f.valid = false;
     hipStream_t s = ctx->stream;
-    for (hipEvent_t& ev : ctx->dbm_ev)
-        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    if (int rc = ensure_events(f.ev)) return rc;
     wfsa::DensePath& dp = *ctx->dense;
-    hipError_t e = dp.byte_marginals_masses(w_full, ctx->dbm_ev, s);
+    hipError_t e = dp.byte_marginals_masses(w_full, f.ev, s);
     if (e == hipErrorOutOfMemory)
         return fail(WFSA_ERR_CAPACITY, "%s: the history of %lld bytes (%d steps x %d row slots x %d states) cannot be allocated", name,
                     (long long)dp.best_paths_history_bytes(), dp.steps(), dp.rows(), dp.np());
@@ -5334,29 +5395,29 @@ int wfsa_dev_dense_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t r
     const int64_t S = ctx->n_strings, B = dp.total_symbols();
     int64_t entries = 0;
     if (rows) {
-        HIP_TRY(dp.byte_marginals_count(&entries, ctx->dbm_ev, s));
+        HIP_TRY(dp.byte_marginals_count(&entries, f.ev, s));
         constexpr int64_t kRowBudget = int64_t(4) << 30;
         if (entries * 12 > kRowBudget)
             return fail(WFSA_ERR_CAPACITY, "%s: the mass rows take %lld bytes (%lld entries of 12 bytes over %lld corpus bytes), over 4 GiB", name,
                         (long long)(entries * 12), (long long)entries, (long long)B);
-        e = dp.byte_marginals_fill(ctx->dbm_ev, s);
+        e = dp.byte_marginals_fill(f.ev, s);
         if (e == hipErrorOutOfMemory)
             return fail(WFSA_ERR_CAPACITY, "%s: the mass rows of %lld bytes cannot be allocated", name, (long long)(entries * 12));
         HIP_TRY(e);
     }
-    if (decode) HIP_TRY(dp.byte_marginals_decode(ctx->dbm_ev, s));
+    if (decode) HIP_TRY(dp.byte_marginals_decode(f.ev, s));
     const std::vector<int64_t>& off = dp.string_offsets();
     std::vector<double> lq(size_t(S), 0.0), sc, plw;
     std::vector<int32_t> codes;
     HIP_TRY(dp.byte_marginals_logq_download(lq.data(), s));
-    ctx->dbm_mrow.clear();
-    ctx->dbm_midx.clear();
-    ctx->dbm_mval.clear();
+    f.rows.row.clear();
+    f.rows.idx.clear();
+    f.rows.val.clear();
     if (rows) {
-        ctx->dbm_mrow = dp.byte_marginals_mrow();
-        ctx->dbm_midx.resize(size_t(entries));
-        ctx->dbm_mval.resize(size_t(entries));
-        HIP_TRY(dp.byte_marginals_rows_download(ctx->dbm_midx.data(), ctx->dbm_mval.data(), s));
+        f.rows.row = dp.byte_marginals_mrow();
+        f.rows.idx.resize(size_t(entries));
+        f.rows.val.resize(size_t(entries));
+        HIP_TRY(dp.byte_marginals_rows_download(f.rows.idx.data(), f.rows.val.data(), s));
     }
     if (decode) {
         sc.assign(size_t(S), 0.0);
@@ -5368,7 +5429,7 @@ int wfsa_dev_dense_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t r
     if (rows) dp.byte_marginals_rows_release();
     auto span = [&](int i, int j, double& out) -> hipError_t {
         float ms = 0.f;
-        const hipError_t r = hipEventElapsedTime(&ms, ctx->dbm_ev[i], ctx->dbm_ev[j]);
+        const hipError_t r = hipEventElapsedTime(&ms, f.ev[i], f.ev[j]);
         out = double(ms);
         return r;
     };
@@ -5385,52 +5446,39 @@ int wfsa_dev_dense_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t r
     ctx->stats.dense_bm_rows_ms = r1 + r2;
     ctx->stats.dense_bm_decode_ms = dc;
     ctx->stats.byte_marginal_ms = fw + bw + (r1 + r2) + dc;
-    ctx->dbm_prow.assign(size_t(S) + 1, 0);
-    ctx->dbm_pidx.clear();
+    f.path.prow.assign(size_t(S) + 1, 0);
+    f.path.pidx.clear();
     if (decode)
         for (int64_t i = 0; i < S; ++i) {
-            if (plw[size_t(i)] > -INFINITY) {
-                const int32_t* cd = codes.data() + 2 * (off[size_t(i)] + i);
-                const int64_t n = 2 * (off[size_t(i) + 1] - off[size_t(i)] + 1);
-                for (int64_t q = 0; q < n; ++q) {
-                    if (cd[q] == wfsa::kCodeNone || cd[q] >= np)
-                        return fail(WFSA_ERR_HIP, "%s: string %lld: code %d at entry %lld is not a path edge", name, (long long)i, int(cd[q]),
-                                    (long long)q);
-                    if (cd[q] >= 0) ctx->dbm_pidx.push_back(cd[q]);
-                }
-            }
-            ctx->dbm_prow[size_t(i) + 1] = int64_t(ctx->dbm_pidx.size());
+            if (plw[size_t(i)] > -INFINITY)
+                if (int rc = expand_codes(ctx, name, i, -1, codes.data() + 2 * (off[size_t(i)] + i), off[size_t(i) + 1] - off[size_t(i)], f.path.pidx))
+                    return rc;
+            f.path.prow[size_t(i) + 1] = int64_t(f.path.pidx.size());
         }
-    ctx->dbm_has_rows = rows != 0;
-    ctx->dbm_has_path = decode != 0;
-    ctx->dbm_valid = true;
+    f.has_rows = rows != 0;
+    f.has_path = decode != 0;
+    f.valid = true;
     if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
     if (decode && score && S > 0) std::memcpy(score, sc.data(), size_t(S) * sizeof(double));
     if (decode && path_logw && S > 0) std::memcpy(path_logw, plw.data(), size_t(S) * sizeof(double));
     if (n_entries) *n_entries = entries;
-    if (n_path_entries) *n_path_entries = int64_t(ctx->dbm_pidx.size());
+    if (n_path_entries) *n_path_entries = int64_t(f.path.pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_dense_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow, int32_t* midx, double* mval) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->dbm_valid)
-        return fail(WFSA_ERR_ARG, "dense_byte_marginals_get: no wfsa_dev_dense_byte_marginals result since the last load");
-    if (!ctx->dbm_has_rows) return fail(WFSA_ERR_ARG, "dense_byte_marginals_get: the last wfsa_dev_dense_byte_marginals call had rows = 0");
-    if (mrow) std::memcpy(mrow, ctx->dbm_mrow.data(), ctx->dbm_mrow.size() * sizeof(int64_t));
-    if (midx && !ctx->dbm_midx.empty()) std::memcpy(midx, ctx->dbm_midx.data(), ctx->dbm_midx.size() * sizeof(int32_t));
-    if (mval && !ctx->dbm_mval.empty()) std::memcpy(mval, ctx->dbm_mval.data(), ctx->dbm_mval.size() * sizeof(double));
+    if (!ctx->dbm.valid) return no_result("dense_byte_marginals", "_get");
+    if (!ctx->dbm.has_rows) return asked_for_none("dense_byte_marginals", "_get", "rows");
+    ctx->dbm.rows.copy_out(mrow, midx, mval);
     return WFSA_OK;
 }
 
 int wfsa_dev_dense_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->dbm_valid)
-        return fail(WFSA_ERR_ARG, "dense_byte_marginals_path_get: no wfsa_dev_dense_byte_marginals result since the last load");
-    if (!ctx->dbm_has_path)
-        return fail(WFSA_ERR_ARG, "dense_byte_marginals_path_get: the last wfsa_dev_dense_byte_marginals call had decode = 0");
-    if (prow) std::memcpy(prow, ctx->dbm_prow.data(), ctx->dbm_prow.size() * sizeof(int64_t));
-    if (pidx && !ctx->dbm_pidx.empty()) std::memcpy(pidx, ctx->dbm_pidx.data(), ctx->dbm_pidx.size() * sizeof(int32_t));
+    if (!ctx->dbm.valid) return no_result("dense_byte_marginals", "_path_get");
+    if (!ctx->dbm.has_path) return asked_for_none("dense_byte_marginals", "_path_get", "decode");
+    ctx->dbm.path.copy_out(nullptr, nullptr, prow, pidx);
     return WFSA_OK;
 }
 
@@ -5456,8 +5504,7 @@ int wfsa_dev_generate(wfsa_dev* ctx, const double* w_full, int64_t n, int32_t ma
     if (n >= (int64_t(1) << 31)) return fail(WFSA_ERR_CAPACITY, "%s: n = %lld samples exceed the per-sample tables", name, (long long)n);
     ctx->gn_valid = false;
     hipStream_t s = ctx->stream;
-    for (hipEvent_t& ev : ctx->gn_ev)
-        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    if (int rc = ensure_events(ctx->gn_ev)) return rc;
     const size_t N = size_t(n);
     const int64_t tiles = wfsa::generate_tiles(n);
     const unsigned zero = 0;
@@ -5578,15 +5625,13 @@ int wfsa_dev_generate_get(wfsa_dev* ctx, uint8_t* sym, int64_t* off, double* log
 int wfsa_dev_posterior_counts(wfsa_dev* ctx, const double* w_full, double* logq, double* entropy, int64_t* n_entries) {
     const char* name = "posterior_counts";
     if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to walk", name);
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
-    if (ctx->dense)
-        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to take its posterior", name);
+    if (int rc = check_loaded(ctx, name, "walk")) return rc;
+    if (int rc = check_tier_weights(ctx, name, nullptr, "take its posterior", w_full)) return rc;
     const int32_t np = ctx->n_params;
-    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
-    DecodeBufs& d = ctx->pc;
-    d.valid = false;
+    auto& f = ctx->pc;
+    DecodeBufs& d = f.d;
+    RowResult& res = f.res;
+    f.valid = false;
     const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end;
     // the longest edge parameter list bounds a count ((max_len + 1) edges a path) and a row; every id indexes the count row
     int64_t max_list = 1;
@@ -5595,8 +5640,8 @@ int wfsa_dev_posterior_counts(wfsa_dev* ctx, const double* w_full, double* logq,
         if (j < 0 || j >= np) return fail(WFSA_ERR_MODEL, "%s: parameter id %d on an edge list is outside 0 .. %d", name, int(j), int(np) - 1);
     const int frac = wfsa::posterior_count_frac((int64_t(ctx->max_len) + 1) * max_list);
     const int64_t wave_bytes = wfsa::posterior_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst, np);
-    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
-    if (fit < 1)
+    const WavePlan wp = wave_plan(ctx, wave_bytes, "WFSA_POSTERIOR_WAVES");
+    if (wp.fit < 1)
         return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations, %d parameters) exceeds the budget",
                     name, (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst, int(np));
     // Room for the rows.  One path uses at most (L + 1) x max_list parameters, but a row is the union over
@@ -5604,87 +5649,53 @@ int wfsa_dev_posterior_counts(wfsa_dev* ctx, const double* w_full, double* logq,
     // counts them (the cursor ends at the exact total), and one more launch at that size fills them in.
     constexpr int64_t kOutBudget = int64_t(4) << 30;   // bytes of ids and values
     const int64_t cap_max = std::max<int64_t>(1, S * int64_t(std::max(np, 1)));
-    int64_t cap = std::min<int64_t>(cap_max, std::max<int64_t>({1, (ctx->total_sym + S) * max_list, int64_t(ctx->pc_idx.n)}));
+    int64_t cap = std::min<int64_t>(cap_max, std::max<int64_t>({1, (ctx->total_sym + S) * max_list, int64_t(f.idx.n)}));
     cap = std::min<int64_t>(cap, kOutBudget / 12);
     int phases = 3;   // WFSA_POSTERIOR_PHASES=1 / 2: timing only (forward pass alone / no row scan), no result
     if (const char* e = std::getenv("WFSA_POSTERIOR_PHASES")) phases = std::max(1, std::min(3, std::atoi(e)));
-    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
-    int64_t max_waves = 16 * int64_t(ctx->n_cu);
-    if (const char* e = std::getenv("WFSA_POSTERIOR_WAVES")) max_waves = std::max<int64_t>(1, std::min<int64_t>(max_waves, std::atoll(e)));
-    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({max_waves, fit, S}));
-    const int grid = int(std::max<int64_t>(1, waves / wpb));
-    const int64_t n_waves = int64_t(grid) * wpb;
     hipStream_t s = ctx->stream;
-    if (!d.ev0) {
-        HIP_TRY(hipEventCreate(&d.ev0));
-        HIP_TRY(hipEventCreate(&d.ev1));
-    }
-    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
-    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    if (int rc = ensure_events(d.ev)) return rc;
     const int64_t hist = int64_t(std::max(ctx->max_len, 1)) * int64_t(std::max(ctx->max_dst, 1));
-    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
+    if (int rc = upload_weights(ctx, d, w_full)) return rc;
     HIP_TRY(d.lw.alloc(size_t(E + X)));
-    HIP_TRY(d.score.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
-    HIP_TRY(ctx->pc_hist.alloc(size_t(n_waves * hist)));
-    HIP_TRY(ctx->pc_gamma.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
-    HIP_TRY(ctx->pc_count.alloc(size_t(n_waves * int64_t(std::max(np, 1)))));
+    HIP_TRY(d.score.alloc(size_t(wp.n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(f.hist.alloc(size_t(wp.n_waves * hist)));
+    HIP_TRY(f.gamma.alloc(size_t(wp.n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(f.count.alloc(size_t(wp.n_waves * int64_t(std::max(np, 1)))));
     HIP_TRY(d.ctr.alloc(1));
-    HIP_TRY(ctx->pc_cursor.alloc(2));
-    HIP_TRY(ctx->pc_logq.alloc(size_t(S)));
-    HIP_TRY(ctx->pc_ent.alloc(size_t(S)));
-    HIP_TRY(ctx->pc_start.alloc(size_t(S)));
-    HIP_TRY(ctx->pc_len.alloc(size_t(S)));
+    HIP_TRY(f.cursor.alloc(2));
+    HIP_TRY(f.logq.alloc(size_t(S)));
+    HIP_TRY(f.ent.alloc(size_t(S)));
+    HIP_TRY(f.start.alloc(size_t(S)));
+    HIP_TRY(f.len.alloc(size_t(S)));
     wfsa::PosteriorArgs a{};
-    a.d.w.c_ptr = ctx->w_cptr.ptr;
-    a.d.w.dst = ctx->w_dst.ptr;
-    a.d.w.e_ptr = ctx->w_eptr.ptr;
-    a.d.w.e_src = ctx->w_esrc.ptr;
-    a.d.w.e_g = ctx->w_eg.ptr;
-    a.d.x_ptr = ctx->x_ptr.ptr;
-    a.d.pptr = ctx->pptr.ptr;
-    a.d.pidx = ctx->pidx.ptr;
-    a.d.n_nodes = ctx->n_nodes;
-    a.d.start = ctx->start;
-    a.d.n_edges = int32_t(E);
-    a.d.n_end = int32_t(X);
-    a.d.sym = ctx->sym.ptr;
-    a.d.off = ctx->off.ptr;
-    a.d.n_strings = int32_t(S);
-    a.d.max_len = ctx->max_len;
-    a.d.max_dst = ctx->max_dst;
-    a.d.k = 1;
-    a.d.wt = d.w.ptr;
-    a.d.lw = d.lw.ptr;
-    a.d.score = d.score.ptr;
-    a.d.back = nullptr;   // (no back-pointers, weights or paths: the rows below instead)
-    a.d.ctr = d.ctr.ptr;
-    a.d.best = nullptr;
-    a.d.path = nullptr;
-    a.hist = ctx->pc_hist.ptr;
-    a.gamma = ctx->pc_gamma.ptr;
-    a.count = ctx->pc_count.ptr;
+    a.d = decode_args(ctx, d);
+    a.d.k = 1;   // (no back-pointers, weights or paths: the rows below instead)
+    a.hist = f.hist.ptr;
+    a.gamma = f.gamma.ptr;
+    a.count = f.count.ptr;
     a.n_params = np;
     a.count_frac = frac;
     a.phases = phases;
-    a.logq = ctx->pc_logq.ptr;
-    a.entropy = ctx->pc_ent.ptr;
-    a.cursor = ctx->pc_cursor.ptr;
-    a.row_start = ctx->pc_start.ptr;
-    a.row_len = ctx->pc_len.ptr;
+    a.logq = f.logq.ptr;
+    a.entropy = f.ent.ptr;
+    a.cursor = f.cursor.ptr;
+    a.row_start = f.start.ptr;
+    a.row_len = f.len.ptr;
     std::vector<double> lq(size_t(S), 0.0), ent(size_t(S), 0.0);
     std::vector<int64_t> start(size_t(S), 0);
     std::vector<int32_t> len(size_t(S), 0);
     unsigned long long cur[2] = {0, 0};
     for (int attempt = 0;; ++attempt) {
-        HIP_TRY(ctx->pc_idx.alloc(size_t(cap)));
-        HIP_TRY(ctx->pc_val.alloc(size_t(cap)));
+        HIP_TRY(f.idx.alloc(size_t(cap)));
+        HIP_TRY(f.val.alloc(size_t(cap)));
         a.capacity = cap;
-        a.out_idx = ctx->pc_idx.ptr;
-        a.out_val = ctx->pc_val.ptr;
-        HIP_TRY(hipEventRecord(d.ev0, s));
-        HIP_TRY(wfsa::launch_posterior_counts(a, grid, wpb, s));
-        HIP_TRY(hipEventRecord(d.ev1, s));
-        HIP_TRY(ctx->pc_cursor.download(cur, 2, s));
+        a.out_idx = f.idx.ptr;
+        a.out_val = f.val.ptr;
+        HIP_TRY(hipEventRecord(d.ev[0], s));
+        HIP_TRY(wfsa::launch_posterior_counts(a, wp.grid, wp.wpb, s));
+        HIP_TRY(hipEventRecord(d.ev[1], s));
+        HIP_TRY(f.cursor.download(cur, 2, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (phases < 3 || cur[1] == 0) break;
         // some row did not fit: the cursor holds the entries all rows need
@@ -5697,52 +5708,50 @@ int wfsa_dev_posterior_counts(wfsa_dev* ctx, const double* w_full, double* logq,
                         (long long)need, (long long)S, int(np), (long long)kOutBudget);
         cap = need;
     }
-    HIP_TRY(ctx->pc_logq.download(lq.data(), size_t(S), s));
-    HIP_TRY(ctx->pc_ent.download(ent.data(), size_t(S), s));
-    HIP_TRY(ctx->pc_start.download(start.data(), size_t(S), s));
-    HIP_TRY(ctx->pc_len.download(len.data(), size_t(S), s));
+    HIP_TRY(f.logq.download(lq.data(), size_t(S), s));
+    HIP_TRY(f.ent.download(ent.data(), size_t(S), s));
+    HIP_TRY(f.start.download(start.data(), size_t(S), s));
+    HIP_TRY(f.len.download(len.data(), size_t(S), s));
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
     ctx->stats.posterior_count_ms = double(ms);
-    ctx->pc_crow.assign(size_t(S) + 1, 0);
-    ctx->pc_cidx.clear();
-    ctx->pc_cval.clear();
+    res.row.assign(size_t(S) + 1, 0);
+    res.idx.clear();
+    res.val.clear();
     if (phases == 3) {
         const size_t total = size_t(cur[0]);
         std::vector<int32_t> idx(total);
         std::vector<double> val(total);
-        HIP_TRY(ctx->pc_idx.download(idx.data(), total, s));
-        HIP_TRY(ctx->pc_val.download(val.data(), total, s));
+        HIP_TRY(f.idx.download(idx.data(), total, s));
+        HIP_TRY(f.val.download(val.data(), total, s));
         HIP_TRY(hipStreamSynchronize(s));
-        ctx->pc_cidx.resize(total);
-        ctx->pc_cval.resize(total);
+        res.idx.resize(total);
+        res.val.resize(total);
         size_t at = 0;
         for (int64_t i = 0; i < S; ++i) {
             const int64_t b = start[size_t(i)], n = len[size_t(i)];
             if (n < 0 || b < 0 || b + n > int64_t(total) || at + size_t(n) > total)
                 return fail(WFSA_ERR_HIP, "%s: string %lld: row [%lld, +%lld) lies outside the %zu entries handed out", name, (long long)i,
                             (long long)b, (long long)n, total);
-            std::copy(idx.begin() + b, idx.begin() + b + n, ctx->pc_cidx.begin() + at);
-            std::copy(val.begin() + b, val.begin() + b + n, ctx->pc_cval.begin() + at);
+            std::copy(idx.begin() + b, idx.begin() + b + n, res.idx.begin() + at);
+            std::copy(val.begin() + b, val.begin() + b + n, res.val.begin() + at);
             at += size_t(n);
-            ctx->pc_crow[size_t(i) + 1] = int64_t(at);
+            res.row[size_t(i) + 1] = int64_t(at);
         }
         if (at != total) return fail(WFSA_ERR_HIP, "%s: the rows hold %zu entries, the cursor handed out %zu", name, at, total);
-        d.valid = true;
+        f.valid = true;
     }
     if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
     if (entropy && S > 0) std::memcpy(entropy, ent.data(), size_t(S) * sizeof(double));
-    if (n_entries) *n_entries = int64_t(ctx->pc_cidx.size());
+    if (n_entries) *n_entries = int64_t(res.idx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_posterior_counts_get(wfsa_dev* ctx, int64_t* crow, int32_t* cidx, double* cval) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->pc.valid) return fail(WFSA_ERR_ARG, "posterior_counts_get: no wfsa_dev_posterior_counts result since the last load");
-    if (crow) std::memcpy(crow, ctx->pc_crow.data(), ctx->pc_crow.size() * sizeof(int64_t));
-    if (cidx && !ctx->pc_cidx.empty()) std::memcpy(cidx, ctx->pc_cidx.data(), ctx->pc_cidx.size() * sizeof(int32_t));
-    if (cval && !ctx->pc_cval.empty()) std::memcpy(cval, ctx->pc_cval.data(), ctx->pc_cval.size() * sizeof(double));
+    if (!ctx->pc.valid) return no_result("posterior_counts", "_get");
+    ctx->pc.res.copy_out(crow, cidx, cval);
     return WFSA_OK;
 }
 
@@ -5754,186 +5763,149 @@ int wfsa_dev_byte_marginals(wfsa_dev* ctx, const double* w_full, int32_t decode,
                             double* path_logw, int64_t* n_entries, int64_t* n_path_entries) {
     const char* name = "byte_marginals";
     if (int rc = check_ctx(ctx)) return rc;
-    if (ctx->mpath) return fail(WFSA_ERR_ARG, "%s: matrix-file mode has no automaton to walk", name);
-    if (!ctx->has_model || !ctx->has_corpus) return fail(WFSA_ERR_ARG, "%s: load a model and a corpus first", name);
-    if (ctx->in_flight) return fail(WFSA_ERR_ARG, "%s: an evaluation is in flight", name);
-    if (ctx->dense)
-        return fail(WFSA_ERR_CAPACITY, "%s: the dense path builds no trellis; load the model with WFSA_DENSE=0 to take its marginals", name);
-    const int32_t np = ctx->n_params;
-    if (!w_full && np > 0) return fail(WFSA_ERR_ARG, "null weights");
+    if (int rc = check_loaded(ctx, name, "walk")) return rc;
+    if (int rc = check_tier_weights(ctx, name, nullptr, "take its marginals", w_full)) return rc;
     const bool dec = decode != 0;
-    DecodeBufs& d = ctx->bm;
-    d.valid = false;
+    auto& f = ctx->bm;
+    DecodeBufs& d = f.d;
+    f.valid = false;
     const int64_t S = ctx->n_strings, E = ctx->n_edges, X = ctx->n_end, T = ctx->total_sym;
     const int64_t wave_bytes = wfsa::marginal_wave_bytes(ctx->max_len, ctx->n_nodes, ctx->max_dst, dec);
-    const int64_t fit = (int64_t(1) << 30) / wave_bytes;
-    if (fit < 1)
+    const WavePlan wp = wave_plan(ctx, wave_bytes, "WFSA_MARGINAL_WAVES");
+    if (wp.fit < 1)
         return fail(WFSA_ERR_CAPACITY, "%s: one string's scratch (%lld bytes: %d nodes, length %d, %d destinations) exceeds the budget", name,
                     (long long)wave_bytes, ctx->n_nodes, ctx->max_len, ctx->max_dst);
     hipStream_t s = ctx->stream;
-    const wfsa::MarginalTables& mt = ctx->bm_tab;
-    if (!ctx->bm_base_ok) {   // once per loaded corpus: where every byte's state sums start
+    const wfsa::MarginalTables& mt = f.tab;
+    if (!f.base_ok) {   // once per loaded corpus: where every byte's state sums start
         std::vector<uint8_t> sym(size_t(std::max<int64_t>(T, 1)));
         HIP_TRY(ctx->sym.download(sym.data(), size_t(T), s));
         HIP_TRY(hipStreamSynchronize(s));
         std::vector<int64_t> base(size_t(T) + 1, 0);
         for (int64_t b = 0; b < T; ++b) base[size_t(b) + 1] = base[size_t(b)] + mt.n_groups(sym[size_t(b)]);
-        HIP_TRY(ctx->bm_base.upload(base.data(), base.size(), s));
+        HIP_TRY(f.base.upload(base.data(), base.size(), s));
         HIP_TRY(hipStreamSynchronize(s));
-        ctx->bm_words = base[size_t(T)];
-        ctx->bm_base_ok = true;
+        f.words = base[size_t(T)];
+        f.base_ok = true;
     }
-    const int64_t words = ctx->bm_words;
+    const int64_t words = f.words;
     constexpr int64_t kMassBudget = int64_t(4) << 30;
     if (words * 8 > kMassBudget)
         return fail(WFSA_ERR_CAPACITY, "%s: the state sums take %lld bytes (%lld corpus bytes), over the %lld-byte budget", name,
                     (long long)(words * 8), (long long)T, (long long)kMassBudget);
-    const int wpb = int(std::min<int64_t>(wfsa::kDecodeWavesPerBlock, fit));
-    int64_t max_waves = 16 * int64_t(ctx->n_cu);
-    if (const char* e = std::getenv("WFSA_MARGINAL_WAVES")) max_waves = std::max<int64_t>(1, std::min<int64_t>(max_waves, std::atoll(e)));
-    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({max_waves, fit, S}));
-    const int grid = int(std::max<int64_t>(1, waves / wpb));
-    const int64_t n_waves = int64_t(grid) * wpb;
-    if (!d.ev0) {
-        HIP_TRY(hipEventCreate(&d.ev0));
-        HIP_TRY(hipEventCreate(&d.ev1));
-    }
-    std::vector<double> hw(size_t(np) + 1, 0.0);   // the zero slot last
-    if (np > 0) std::memcpy(hw.data(), w_full, size_t(np) * sizeof(double));
+    if (int rc = ensure_events(d.ev)) return rc;
     const int64_t hist = int64_t(std::max(ctx->max_len, 1)) * int64_t(std::max(ctx->max_dst, 1));
     const size_t n_path = size_t(T + S);
-    HIP_TRY(d.w.upload(hw.data(), hw.size(), s));
+    if (int rc = upload_weights(ctx, d, w_full)) return rc;
     HIP_TRY(d.lw.alloc(size_t(E + X)));
-    HIP_TRY(d.score.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
-    HIP_TRY(ctx->bm_hist.alloc(size_t(n_waves * hist)));
-    HIP_TRY(ctx->bm_gamma.alloc(size_t(n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(d.score.alloc(size_t(wp.n_waves * 2 * int64_t(ctx->n_nodes))));
+    HIP_TRY(f.hist.alloc(size_t(wp.n_waves * hist)));
+    HIP_TRY(f.gamma.alloc(size_t(wp.n_waves * 2 * int64_t(ctx->n_nodes))));
     HIP_TRY(d.ctr.alloc(1));
-    HIP_TRY(ctx->bm_mass.alloc(size_t(words)));
-    HIP_TRY(ctx->bm_logq.alloc(size_t(S)));
-    HIP_TRY(ctx->bm_bound.alloc(size_t(T)));
+    HIP_TRY(f.mass.alloc(size_t(words)));
+    HIP_TRY(f.logq.alloc(size_t(S)));
+    HIP_TRY(f.bound.alloc(size_t(T)));
     if (dec) {
-        HIP_TRY(d.back.alloc(size_t(n_waves * hist)));
+        HIP_TRY(d.back.alloc(size_t(wp.n_waves * hist)));
         HIP_TRY(d.best.alloc(size_t(S)));
         HIP_TRY(d.path.alloc(n_path));
-        HIP_TRY(ctx->bm_score.alloc(size_t(S)));
+        HIP_TRY(f.score.alloc(size_t(S)));
     }
     wfsa::MarginalArgs a{};
-    a.d.w.c_ptr = ctx->w_cptr.ptr;
-    a.d.w.dst = ctx->w_dst.ptr;
-    a.d.w.e_ptr = ctx->w_eptr.ptr;
-    a.d.w.e_src = ctx->w_esrc.ptr;
-    a.d.w.e_g = ctx->w_eg.ptr;
-    a.d.x_ptr = ctx->x_ptr.ptr;
-    a.d.pptr = ctx->pptr.ptr;
-    a.d.pidx = ctx->pidx.ptr;
-    a.d.n_nodes = ctx->n_nodes;
-    a.d.start = ctx->start;
-    a.d.n_edges = int32_t(E);
-    a.d.n_end = int32_t(X);
-    a.d.sym = ctx->sym.ptr;
-    a.d.off = ctx->off.ptr;
-    a.d.n_strings = int32_t(S);
-    a.d.max_len = ctx->max_len;
-    a.d.max_dst = ctx->max_dst;
+    a.d = decode_args(ctx, d);
     a.d.k = 1;
-    a.d.wt = d.w.ptr;
-    a.d.lw = d.lw.ptr;
-    a.d.score = d.score.ptr;
     a.d.back = dec ? d.back.ptr : nullptr;
-    a.d.ctr = d.ctr.ptr;
     a.d.best = dec ? d.best.ptr : nullptr;
     a.d.path = dec ? d.path.ptr : nullptr;
-    a.hist = ctx->bm_hist.ptr;
-    a.gamma = ctx->bm_gamma.ptr;
+    a.hist = f.hist.ptr;
+    a.gamma = f.gamma.ptr;
     a.n_states = ctx->h_tm->n_states;
-    a.ord = ctx->bm_ord.ptr;
-    a.seg = ctx->bm_seg.ptr;
-    a.grp = ctx->bm_grp.ptr;
-    a.base = ctx->bm_base.ptr;
-    a.mass = ctx->bm_mass.ptr;
-    a.logq = ctx->bm_logq.ptr;
-    a.boundary = ctx->bm_bound.ptr;
-    a.mea_score = dec ? ctx->bm_score.ptr : nullptr;
-    HIP_TRY(hipEventRecord(d.ev0, s));
-    HIP_TRY(wfsa::launch_marginal_rows(a, words, grid, wpb, s));
-    if (dec) HIP_TRY(wfsa::launch_marginal_decode(a, grid, wpb, s));
-    HIP_TRY(hipEventRecord(d.ev1, s));
+    a.ord = f.ord.ptr;
+    a.seg = f.seg.ptr;
+    a.grp = f.grp.ptr;
+    a.base = f.base.ptr;
+    a.mass = f.mass.ptr;
+    a.logq = f.logq.ptr;
+    a.boundary = f.bound.ptr;
+    a.mea_score = dec ? f.score.ptr : nullptr;
+    HIP_TRY(hipEventRecord(d.ev[0], s));
+    HIP_TRY(wfsa::launch_marginal_rows(a, words, wp.grid, wp.wpb, s));
+    if (dec) HIP_TRY(wfsa::launch_marginal_decode(a, wp.grid, wp.wpb, s));
+    HIP_TRY(hipEventRecord(d.ev[1], s));
     std::vector<double> lq(size_t(S), 0.0), bound(size_t(T), 0.0), sc, plw;
     std::vector<unsigned long long> mass(static_cast<size_t>(words));
     std::vector<int64_t> off(size_t(S) + 1), base(size_t(T) + 1);
     std::vector<uint8_t> sym(size_t(std::max<int64_t>(T, 1)));
     std::vector<int32_t> path;
-    HIP_TRY(ctx->bm_logq.download(lq.data(), size_t(S), s));
-    HIP_TRY(ctx->bm_bound.download(bound.data(), size_t(T), s));
-    HIP_TRY(ctx->bm_mass.download(mass.data(), size_t(words), s));
-    HIP_TRY(ctx->bm_base.download(base.data(), size_t(T) + 1, s));
+    HIP_TRY(f.logq.download(lq.data(), size_t(S), s));
+    HIP_TRY(f.bound.download(bound.data(), size_t(T), s));
+    HIP_TRY(f.mass.download(mass.data(), size_t(words), s));
+    HIP_TRY(f.base.download(base.data(), size_t(T) + 1, s));
     HIP_TRY(ctx->sym.download(sym.data(), size_t(T), s));
     HIP_TRY(ctx->off.download(off.data(), size_t(S) + 1, s));
     if (dec) {
         sc.resize(size_t(S));
         plw.resize(size_t(S));
         path.resize(n_path);
-        HIP_TRY(ctx->bm_score.download(sc.data(), size_t(S), s));
+        HIP_TRY(f.score.download(sc.data(), size_t(S), s));
         HIP_TRY(d.best.download(plw.data(), size_t(S), s));
         HIP_TRY(d.path.download(path.data(), n_path, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    HIP_TRY(hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
     ctx->stats.byte_marginal_ms = double(ms);
     // the rows: per corpus byte the groups whose fixed-point sum is not 0, as state ids (ascending: the groups ascend by owner)
-    ctx->bm_mrow.assign(size_t(T) + 1, 0);
-    ctx->bm_midx.clear();
-    ctx->bm_mval.clear();
+    RowResult& rows = f.rows;
+    rows.row.assign(size_t(T) + 1, 0);
+    rows.idx.clear();
+    rows.val.clear();
     const size_t listed = size_t(std::count_if(mass.begin(), mass.end(), [](unsigned long long v) { return v != 0ull; }));
-    ctx->bm_midx.reserve(listed);
-    ctx->bm_mval.reserve(listed);
+    rows.idx.reserve(listed);
+    rows.val.reserve(listed);
     for (int64_t b = 0; b < T; ++b) {
         const int c = sym[size_t(b)];
         const int32_t* st = mt.g_state.data() + mt.g_ptr[size_t(c)];
         const unsigned long long* wd = mass.data() + base[size_t(b)];
         for (int32_t g = 0; g < mt.n_groups(c); ++g)
             if (wd[g] != 0ull) {
-                ctx->bm_midx.push_back(st[g]);
-                ctx->bm_mval.push_back(std::ldexp(double(wd[g]), -wfsa::kMarginalFrac));
+                rows.idx.push_back(st[g]);
+                rows.val.push_back(std::ldexp(double(wd[g]), -wfsa::kMarginalFrac));
             }
-        ctx->bm_mrow[size_t(b) + 1] = int64_t(ctx->bm_midx.size());
+        rows.row[size_t(b) + 1] = int64_t(rows.idx.size());
     }
-    ctx->bm_prow.assign(size_t(S) + 1, 0);
-    ctx->bm_pidx.clear();
+    f.path.prow.assign(size_t(S) + 1, 0);
+    f.path.pidx.clear();
     if (dec)
         for (int64_t i = 0; i < S; ++i) {
             const int32_t* pe = path.data() + off[size_t(i)] + i;
             if (pe[0] >= 0)
-                if (int rc = expand_path(ctx, name, i, -1, pe, off[size_t(i) + 1] - off[size_t(i)], ctx->bm_pidx)) return rc;
-            ctx->bm_prow[size_t(i) + 1] = int64_t(ctx->bm_pidx.size());
+                if (int rc = expand_path(ctx, name, i, -1, pe, off[size_t(i) + 1] - off[size_t(i)], f.path.pidx)) return rc;
+            f.path.prow[size_t(i) + 1] = int64_t(f.path.pidx.size());
         }
-    ctx->bm_has_path = dec;
-    d.valid = true;
+    f.has_path = dec;
+    f.valid = true;
     if (logq && S > 0) std::memcpy(logq, lq.data(), size_t(S) * sizeof(double));
     if (boundary && T > 0) std::memcpy(boundary, bound.data(), size_t(T) * sizeof(double));
     if (dec && score && S > 0) std::memcpy(score, sc.data(), size_t(S) * sizeof(double));
     if (dec && path_logw && S > 0) std::memcpy(path_logw, plw.data(), size_t(S) * sizeof(double));
-    if (n_entries) *n_entries = int64_t(ctx->bm_midx.size());
-    if (n_path_entries) *n_path_entries = int64_t(ctx->bm_pidx.size());
+    if (n_entries) *n_entries = int64_t(rows.idx.size());
+    if (n_path_entries) *n_path_entries = int64_t(f.path.pidx.size());
     return WFSA_OK;
 }
 
 int wfsa_dev_byte_marginals_get(wfsa_dev* ctx, int64_t* mrow, int32_t* midx, double* mval) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->bm.valid) return fail(WFSA_ERR_ARG, "byte_marginals_get: no wfsa_dev_byte_marginals result since the last load");
-    if (mrow) std::memcpy(mrow, ctx->bm_mrow.data(), ctx->bm_mrow.size() * sizeof(int64_t));
-    if (midx && !ctx->bm_midx.empty()) std::memcpy(midx, ctx->bm_midx.data(), ctx->bm_midx.size() * sizeof(int32_t));
-    if (mval && !ctx->bm_mval.empty()) std::memcpy(mval, ctx->bm_mval.data(), ctx->bm_mval.size() * sizeof(double));
+    if (!ctx->bm.valid) return no_result("byte_marginals", "_get");
+    ctx->bm.rows.copy_out(mrow, midx, mval);
     return WFSA_OK;
 }
 
 int wfsa_dev_byte_marginals_path_get(wfsa_dev* ctx, int64_t* prow, int32_t* pidx) {
     if (!ctx) return fail(WFSA_ERR_ARG, "null context");
-    if (!ctx->bm.valid) return fail(WFSA_ERR_ARG, "byte_marginals_path_get: no wfsa_dev_byte_marginals result since the last load");
-    if (!ctx->bm_has_path) return fail(WFSA_ERR_ARG, "byte_marginals_path_get: the last wfsa_dev_byte_marginals call had decode = 0");
-    if (prow) std::memcpy(prow, ctx->bm_prow.data(), ctx->bm_prow.size() * sizeof(int64_t));
-    if (pidx && !ctx->bm_pidx.empty()) std::memcpy(pidx, ctx->bm_pidx.data(), ctx->bm_pidx.size() * sizeof(int32_t));
+    if (!ctx->bm.valid) return no_result("byte_marginals", "_path_get");
+    if (!ctx->bm.has_path) return asked_for_none("byte_marginals", "_path_get", "decode");
+    ctx->bm.path.copy_out(nullptr, nullptr, prow, pidx);
     return WFSA_OK;
 }
 
